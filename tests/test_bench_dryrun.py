@@ -17,7 +17,7 @@ REPO = Path(__file__).resolve().parent.parent
 
 
 @pytest.mark.parametrize("world", [2, 4, 8])
-def test_bench_dry_run_world(world):
+def test_bench_dry_run_world(world, tmp_path):
     port = 29580 + world
     cmd = [
         sys.executable,
@@ -37,6 +37,8 @@ def test_bench_dry_run_world(world):
         "--backend",
         "gloo",
         "--dry-run",
+        "--dump-outputs",
+        str(tmp_path / "dump"),
     ]
     out = subprocess.run(
         cmd, capture_output=True, text=True, timeout=300, cwd=str(REPO)
@@ -51,3 +53,11 @@ def test_bench_dry_run_world(world):
     assert rec["config"]["parallelism"] == f"shard{world}"
     assert rec["config"]["dry_run"] is True
     assert rec["steps"] == 2
+    assert rec["ms_per_step"] > 0
+    # rank 0 alone writes what the last timed step returned
+    import numpy as np
+
+    verdict = np.load(tmp_path / "dump" / "bls_verdict.npy")
+    root = np.load(tmp_path / "dump" / "state_root.npy")
+    assert verdict.dtype == np.float32 and verdict.tolist() == [1.0]
+    assert root.dtype == np.float32 and root.shape == (32,)

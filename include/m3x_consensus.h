@@ -40,6 +40,8 @@ typedef struct m3x_ctx m3x_ctx;
 #define M3X_ERR_HIP -1      /* HIP runtime failure */
 #define M3X_ERR_ARG -2      /* bad argument */
 #define M3X_ERR_NOMEM -3
+#define M3X_ERR_ENCODING -4 /* malformed point / non-canonical field element
+                               (c_kzg::Error analogue) */
 
 int32_t m3x_ctx_create(m3x_ctx **out, int32_t device);
 void m3x_ctx_destroy(m3x_ctx *ctx);
@@ -49,7 +51,8 @@ int32_t m3x_abi_version(void);
 /* per-kernel HIP-event timing (for benchmarks/roofline): enable resets the
  * accumulators; kernel ids are the M3X_K_* slots (0 leaves, 1 reduce,
  * 2 finalize, 3 bls_prepare, 4 bls_h2c, 5 bls_miller, 6 bls_reduce,
- * 7 bls_finish). */
+ * 7 bls_finish, 8 bls_agg, 9 kzg_challenge, 10 kzg_decomp, 11 kzg_eval,
+ * 12 kzg_batch_r, 13 kzg_mults, 14 kzg_reduce, 15 kzg_finish). */
 int32_t m3x_timing_enable(m3x_ctx *ctx, int32_t on);
 int32_t m3x_kernel_ms(m3x_ctx *ctx, int32_t kernel_id, double *ms,
                       uint64_t *launches);
@@ -182,6 +185,63 @@ int32_t m3x_bls_verify_sets_dev(m3x_ctx *ctx, const void *msgs_dev,
                                 const void *sigs_dev, const void *pks_dev,
                                 const void *pk_offsets_dev,
                                 const void *rands_dev, uint64_t n);
+
+/* ---- KZG blob proof verification (Deneb; crypto/kzg/src/lib.rs) ----
+ *
+ * Big-endian everywhere: commitments/proofs are 48B compressed G1 (infinity
+ * 0xc0... is valid), z/y are 32B canonical scalars, a blob is 4096 x 32B
+ * canonical scalars. Verify calls return 1 valid / 0 invalid / <0 error; a
+ * failed proof is 0, never an error. A malformed point, a point outside
+ * the subgroup or a scalar >= r is M3X_ERR_ENCODING. n == 0 returns 1.
+ * The check is the batch equation
+ *   e(sum r^i pi_i, -[tau]G2) *
+ *   e(sum r^i (C_i - y_i G1) + sum r^i z_i pi_i, G2) == 1
+ * with r from the spec's RCKZGBATCH___V1_ transcript (n == 1 included). */
+typedef struct m3x_kzg m3x_kzg;
+
+/* Kzg::new_from_trusted_setup (lib.rs:62-70), verification part only: the
+ * one setup point verification needs is [tau]G2 = g2_monomial[1], 96B
+ * compressed. Validated on the device (on curve, in the subgroup, not
+ * infinity; else M3X_ERR_ENCODING); -[tau]G2 stays in device memory. */
+int32_t m3x_kzg_create(m3x_ctx *ctx, const uint8_t g2_tau[96],
+                       m3x_kzg **out);
+void m3x_kzg_destroy(m3x_kzg *kzg);
+
+/* Kzg::verify_kzg_proof (lib.rs:152-167) */
+int32_t m3x_kzg_verify_proof(m3x_ctx *ctx, m3x_kzg *kzg, const uint8_t c[48],
+                             const uint8_t z[32], const uint8_t y[32],
+                             const uint8_t proof[48]);
+/* verify_kzg_proof_batch of the spec (what lib.rs:105-132 reaches inside
+ * c-kzg once z, y are known): cs/proofs n*48, zs/ys n*32 */
+int32_t m3x_kzg_verify_proof_batch(m3x_ctx *ctx, m3x_kzg *kzg,
+                                   const uint8_t *cs, const uint8_t *zs,
+                                   const uint8_t *ys, const uint8_t *proofs,
+                                   uint64_t n);
+/* Kzg::verify_blob_kzg_proof (lib.rs:83-103) with n == 1 and
+ * Kzg::verify_blob_kzg_proof_batch (lib.rs:105-132): blobs n*131072 */
+int32_t m3x_kzg_verify_blob_proof_batch(m3x_ctx *ctx, m3x_kzg *kzg,
+                                        const uint8_t *blobs,
+                                        const uint8_t *cs,
+                                        const uint8_t *proofs, uint64_t n);
+/* same, all three inputs already in device memory */
+int32_t m3x_kzg_verify_blob_proof_batch_dev(m3x_ctx *ctx, m3x_kzg *kzg,
+                                            const void *blobs_dev,
+                                            const void *cs_dev,
+                                            const void *proofs_dev,
+                                            uint64_t n);
+
+/* test/introspection seams (like m3x_bls_h2c_test; not on the hot path).
+ * blob_challenge_eval: z_i = compute_challenge(blob_i, c_i) (or zs_in[i]
+ * when zs_in != NULL) and y_i = blob_i's polynomial at z_i; out_z/out_y
+ * n*32. batch_challenge_test: the verify_kzg_proof_batch challenge r. */
+int32_t m3x_kzg_blob_challenge_eval(m3x_ctx *ctx, const uint8_t *blobs,
+                                    const uint8_t *cs, const uint8_t *zs_in,
+                                    uint64_t n, uint8_t *out_z,
+                                    uint8_t *out_y);
+int32_t m3x_kzg_batch_challenge_test(m3x_ctx *ctx, const uint8_t *cs,
+                                     const uint8_t *zs, const uint8_t *ys,
+                                     const uint8_t *proofs, uint64_t n,
+                                     uint8_t out_r[32]);
 
 #ifdef __cplusplus
 }

@@ -214,6 +214,45 @@ def _bind(lib):
                 ctypes.c_uint64,
             ],
         ),
+        (
+            "m3x_kzg_create",
+            [ctypes.c_void_p, ctypes.c_char_p,
+             ctypes.POINTER(ctypes.c_void_p)],
+        ),
+        ("m3x_kzg_destroy", [ctypes.c_void_p]),
+        (
+            "m3x_kzg_verify_proof",
+            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p,
+             ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p],
+        ),
+        (
+            "m3x_kzg_verify_proof_batch",
+            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p,
+             ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
+             ctypes.c_uint64],
+        ),
+        (
+            "m3x_kzg_verify_blob_proof_batch",
+            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p,
+             ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint64],
+        ),
+        (
+            "m3x_kzg_verify_blob_proof_batch_dev",
+            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64],
+        ),
+        (
+            "m3x_kzg_blob_challenge_eval",
+            [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p,
+             ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p,
+             ctypes.c_char_p],
+        ),
+        (
+            "m3x_kzg_batch_challenge_test",
+            [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p,
+             ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint64,
+             ctypes.c_char_p],
+        ),
     ]:
         try:
             fn = getattr(lib, name)
@@ -221,7 +260,9 @@ def _bind(lib):
             continue
         fn.argtypes = argtypes
         fn.restype = (
-            None if name == "m3x_registry_cache_destroy" else ctypes.c_int32
+            None
+            if name in ("m3x_registry_cache_destroy", "m3x_kzg_destroy")
+            else ctypes.c_int32
         )
     return lib
 
@@ -307,6 +348,13 @@ class Ctx:
         "bls_reduce",
         "bls_finish",
         "bls_agg",
+        "kzg_challenge",
+        "kzg_decomp",
+        "kzg_eval",
+        "kzg_batch_r",
+        "kzg_mults",
+        "kzg_reduce",
+        "kzg_finish",
     ]
 
     def kernel_times(self):

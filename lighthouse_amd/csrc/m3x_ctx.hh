@@ -15,7 +15,14 @@ enum m3x_kernel_id {
   M3X_K_BLS_REDUCE = 6,
   M3X_K_BLS_FINISH = 7,
   M3X_K_BLS_AGG = 8,
-  M3X_K_COUNT = 9
+  M3X_K_KZG_CHALLENGE = 9, // per-blob Fiat-Shamir hash (stream2)
+  M3X_K_KZG_DECOMP = 10,   // commitment/proof decompress + subgroup check
+  M3X_K_KZG_EVAL = 11,     // blob evaluation at z
+  M3X_K_KZG_BATCH_R = 12,  // batch challenge + scalar powers
+  M3X_K_KZG_MULTS = 13,    // G1 scalar multiplications
+  M3X_K_KZG_REDUCE = 14,   // G1 sums
+  M3X_K_KZG_FINISH = 15,   // pairing check
+  M3X_K_COUNT = 16
 };
 
 struct m3x_ctx {

@@ -1,0 +1,774 @@
+// MI355X-native KZG blob proof verification (Deneb polynomial-commitments.md
+// verify_kzg_proof / verify_blob_kzg_proof / verify_blob_kzg_proof_batch;
+// the reference's crypto/kzg/src/lib.rs:83-167 surface).
+//
+// Pipeline for n (blob, commitment, proof) triples, big-endian everywhere:
+//   k_kzg_challenge  z_i = SHA256(domain | degree | blob_i | C_i) mod r —
+//                    one lane per blob, on stream2
+//   k_kzg_decomp     decompress + subgroup-check every C_i and pi_i (2n
+//                    lanes); independent of z, so it overlaps the hash
+//   k_kzg_eval       y_i = p_i(z_i), barycentric over the bit-reversed
+//                    4096th roots of unity, one 256-thread block per blob
+//   k_kzg_batch_r    r = SHA256(domain | 4096 | n | C_i z_i y_i pi_i ...)
+//                    mod r and the scalars r^i, r^i z_i, -sum r^i y_i
+//   k_kzg_mults      the 3n+1 independent 255-bit G1 scalar mults, one
+//                    lane each
+//   k_kzg_reduce_g1  two-stage Jacobian sums (k_bls_reduce_sig's shape)
+//   k_kzg_finish     one wave:
+//        e(sum r^i pi_i, -[tau]G2) *
+//        e(sum r^i (C_i - y_i G1) + sum r^i z_i pi_i, G2) == 1
+// The batch equation is used for n == 1 too (r^0 = 1): it is algebraically
+// the spec's single-proof check and needs no G2 scalar multiplication.
+// Integer VALU workload (no MFMA); Fp/G1/pairing code is bls_device.hh's.
+#include "bls_device.hh"
+#include "fr_device.hh"
+#include "m3x_ctx.hh"
+#include "../../include/m3x_consensus.h"
+
+using namespace m3xb;
+using namespace m3xf;
+
+#define KZG_N 4096
+#define KZG_BLOB_BYTES 131072
+#define KZG_MAX_BATCH 65535 // one grid dimension; far above any block's blobs
+
+// validated setup: device-resident G2 points of the pairing check
+struct m3x_kzg {
+  int device = 0;
+  g2j *g2 = nullptr; // [0] = -[tau]G2, [1] = G2 generator (z = 1)
+};
+
+namespace {
+
+struct KzgWork {
+  uint8_t *zs;     // [n*32] challenges, canonical BE
+  uint8_t *ys;     // [n*32] evaluations, canonical BE
+  uint8_t *tr;     // [32+160n] batch-challenge transcript
+  uint8_t *sc;     // [(2n+1)*32] BE scalars: r^i | r^i z_i | -sum r^i y_i
+  uint8_t *r_out;  // [32] the batch challenge
+  g1j *pts;        // [2n] validated commitments, then proofs (z=0: infinity)
+  g1j *terms;      // [3n+1] r^i pi_i | r^i z_i pi_i | r^i C_i | -(sum r^i y_i)G1
+  g1j *stage;      // [512] stage-1 partial sums (two reductions)
+  g1j *sums;       // [2] pairing arguments
+  int *fail;       // [1] encoding-error flag
+  int *verdict;    // [1]
+};
+
+__device__ __forceinline__ uint32_t ld_be32(const uint8_t *p) {
+  uint32_t v;
+  __builtin_memcpy(&v, p, 4);
+  return __builtin_bswap32(v);
+}
+
+__device__ __forceinline__ void g1j_set_inf(g1j &p) {
+  fp_zero(p.x);
+  fp_zero(p.y);
+  fp_zero(p.z);
+}
+
+// "FSBLOBVERIFY_V1_" / "RCKZGBATCH___V1_" as big-endian words / bytes
+__device__ __constant__ static const uint32_t KZG_FS_DOMAIN[4] = {
+    0x4653424cu, 0x4f425645u, 0x52494659u, 0x5f56315fu};
+__device__ __constant__ static const uint8_t KZG_RC_DOMAIN[16] = {
+    'R', 'C', 'K', 'Z', 'G', 'B', 'A', 'T', 'C', 'H', '_', '_', '_', 'V', '1', '_'};
+
+// ---------------------------------------------------------------- kernels
+
+// compute_challenge: the 131152-byte message is 2050 compressions; block 0
+// is domain | BE128(4096) | blob[0:32], so every later block reads the
+// blob at a 32-byte offset. SHA-256 of one message is serial: one lane.
+__global__ __launch_bounds__(64) void k_kzg_challenge(
+    const uint8_t *__restrict__ blobs, const uint8_t *__restrict__ cs,
+    uint64_t n, KzgWork w) {
+  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint8_t *blob = blobs + i * KZG_BLOB_BYTES;
+  const uint8_t *c = cs + 48 * i;
+  m3x::Sha256State s;
+  m3x::sha256_init(s);
+  uint32_t m[16];
+#pragma unroll
+  for (int k = 0; k < 4; k++) m[k] = KZG_FS_DOMAIN[k];
+  m[4] = 0;
+  m[5] = 0;
+  m[6] = 0;
+  m[7] = KZG_N;
+#pragma unroll
+  for (int k = 0; k < 8; k++) m[8 + k] = ld_be32(blob + 4 * k);
+  m3x::sha256_compress(s, m);
+  for (uint32_t b = 1; b < 2048; b++) {
+    const uint8_t *p = blob + 64 * b - 32;
+#pragma unroll
+    for (int k = 0; k < 16; k++) m[k] = ld_be32(p + 4 * k);
+    m3x::sha256_compress(s, m);
+  }
+#pragma unroll
+  for (int k = 0; k < 8; k++)
+    m[k] = ld_be32(blob + KZG_BLOB_BYTES - 32 + 4 * k);
+#pragma unroll
+  for (int k = 0; k < 8; k++) m[8 + k] = ld_be32(c + 4 * k);
+  m3x::sha256_compress(s, m);
+#pragma unroll
+  for (int k = 0; k < 4; k++) m[k] = ld_be32(c + 32 + 4 * k);
+  m[4] = 0x80000000u;
+#pragma unroll
+  for (int k = 5; k < 15; k++) m[k] = 0;
+  m[15] = (32 + KZG_BLOB_BYTES + 48) * 8;
+  m3x::sha256_compress(s, m);
+  uint8_t dg[32];
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    dg[4 * k] = (uint8_t)(s.h[k] >> 24);
+    dg[4 * k + 1] = (uint8_t)(s.h[k] >> 16);
+    dg[4 * k + 2] = (uint8_t)(s.h[k] >> 8);
+    dg[4 * k + 3] = (uint8_t)s.h[k];
+  }
+  fr z;
+  fr_from_be32_reduce(z, dg);
+  fr_to_be32(z, w.zs + 32 * i);
+}
+
+__device__ __forceinline__ uint32_t bitrev_lo(uint32_t v, int bits) {
+  return __builtin_bitreverse32(v) >> (32 - bits);
+}
+
+// evaluate_polynomial_in_evaluation_form: one block per blob, thread t owns
+// elements 16t..16t+15. bitrev12(16t+k) = bitrev4(k)<<8 | bitrev8(t), so the
+// thread's roots are omega^bitrev8(t) * (omega^256)^bitrev4(k): one 8-bit
+// power and 15 multiplies, no table. The 16 denominators z - omega_j share
+// one Fermat inversion (Montgomery's trick).
+__global__ __launch_bounds__(256) void k_kzg_eval(
+    const uint8_t *__restrict__ blobs, uint64_t n, KzgWork w) {
+  __shared__ fr lds[256];
+  __shared__ fr s_hitval;
+  __shared__ int s_hit;
+  uint64_t b = blockIdx.x;
+  int t = threadIdx.x;
+  if (b >= n) return;
+  const uint8_t *blob = blobs + b * KZG_BLOB_BYTES;
+  if (t == 0) s_hit = 0;
+  __syncthreads();
+  fr z;
+  if (!fr_from_be32(z, w.zs + 32 * b)) { // block-uniform
+    if (t == 0) atomicOr(w.fail, 1);
+    return;
+  }
+  fr omega, w16, base;
+#pragma unroll
+  for (int i = 0; i < 8; i++) omega.v[i] = FR_OMEGA_MONT[i];
+  w16 = omega;
+  for (int i = 0; i < 8; i++) fr_sqr(w16, w16); // omega^256
+  uint32_t e = bitrev_lo((uint32_t)t, 8);
+  fr_pow(base, omega, &e, 1);
+  fr num[16], den[16], pre[16];
+  fr g, run;
+  fr_one(g);
+  fr_one(run);
+  bool bad = false;
+  for (int mi = 0; mi < 16; mi++) {
+    int k = (int)bitrev_lo((uint32_t)mi, 4);
+    uint32_t j = 16u * (uint32_t)t + (uint32_t)k;
+    fr f, wk, d;
+    if (!fr_from_be32(f, blob + 32 * j)) {
+      bad = true;
+      fr_zero(f);
+    }
+    fr_mul(wk, base, g); // omega^bitrev12(j)
+    fr_mul(g, g, w16);
+    fr_sub(d, z, wk);
+    if (fr_is_zero(d)) { // z is in the domain: y = f_j, no division
+      s_hitval = f;
+      s_hit = 1;
+      fr_one(d);
+    }
+    fr_mul(num[mi], f, wk);
+    den[mi] = d;
+    fr_mul(run, run, d);
+    pre[mi] = run;
+  }
+  if (bad) atomicOr(w.fail, 1);
+  fr inv, acc;
+  fr_inv(inv, run);
+  fr_zero(acc);
+  for (int mi = 15; mi >= 0; mi--) {
+    fr id, term;
+    if (mi > 0)
+      fr_mul(id, inv, pre[mi - 1]);
+    else
+      id = inv;
+    fr_mul(inv, inv, den[mi]);
+    fr_mul(term, num[mi], id);
+    fr_add(acc, acc, term);
+  }
+  lds[t] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s) {
+      fr a;
+      fr_add(a, lds[t], lds[t + s]);
+      lds[t] = a;
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    fr y;
+    if (s_hit) {
+      y = s_hitval;
+    } else {
+      fr zn, one, ninv;
+      zn = z;
+      for (int i = 0; i < 12; i++) fr_sqr(zn, zn); // z^4096
+      fr_one(one);
+      fr_sub(zn, zn, one);
+#pragma unroll
+      for (int i = 0; i < 8; i++) ninv.v[i] = FR_N_INV_MONT[i];
+      fr_mul(y, lds[0], zn);
+      fr_mul(y, y, ninv);
+    }
+    fr_to_be32(y, w.ys + 32 * b);
+  }
+}
+
+// verify_kzg_proof_batch's challenge and its powers. The block assembles
+// the transcript in parallel; lane 0 hashes it and walks the powers.
+__global__ __launch_bounds__(256) void k_kzg_batch_r(
+    const uint8_t *__restrict__ cs, const uint8_t *__restrict__ proofs,
+    uint64_t n, KzgWork w) {
+  uint32_t len = 32 + 160 * (uint32_t)n;
+  for (uint32_t idx = threadIdx.x; idx < len; idx += blockDim.x) {
+    uint8_t v;
+    if (idx < 16) {
+      v = KZG_RC_DOMAIN[idx];
+    } else if (idx < 24) {
+      v = (uint8_t)((uint64_t)KZG_N >> (8 * (23 - idx)));
+    } else if (idx < 32) {
+      v = (uint8_t)(n >> (8 * (31 - idx)));
+    } else {
+      uint32_t q = (idx - 32) / 160, o = (idx - 32) % 160;
+      if (o < 48)
+        v = cs[48 * q + o];
+      else if (o < 80)
+        v = w.zs[32 * q + (o - 48)];
+      else if (o < 112)
+        v = w.ys[32 * q + (o - 80)];
+      else
+        v = proofs[48 * q + (o - 112)];
+    }
+    w.tr[idx] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  uint8_t dg[32];
+  m3x::sha256_bytes(w.tr, len, dg);
+  fr rr, pw, sy;
+  fr_from_be32_reduce(rr, dg);
+  fr_to_be32(rr, w.r_out);
+  fr_one(pw);
+  fr_zero(sy);
+  bool bad = false;
+  for (uint64_t i = 0; i < n; i++) {
+    fr z, y, t;
+    if (!fr_from_be32(z, w.zs + 32 * i) || !fr_from_be32(y, w.ys + 32 * i)) {
+      bad = true; // out-of-range z or y
+      fr_zero(z);
+      fr_zero(y);
+    }
+    fr_to_be32(pw, w.sc + 32 * i);
+    fr_mul(t, pw, z);
+    fr_to_be32(t, w.sc + 32 * (n + i));
+    fr_mul(t, pw, y);
+    fr_add(sy, sy, t);
+    fr_mul(pw, pw, rr);
+  }
+  fr_neg(sy, sy);
+  fr_to_be32(sy, w.sc + 32 * (2 * n));
+  if (bad) atomicOr(w.fail, 1);
+}
+
+// validate_kzg_g1 for every commitment and proof: decompress (infinity is
+// a valid KZG point, unlike a public key) + subgroup check as in
+// k_bls_pk_decompress. One lane per point.
+__global__ __launch_bounds__(64, 1) void k_kzg_decomp(
+    const uint8_t *__restrict__ cs, const uint8_t *__restrict__ proofs,
+    uint64_t n, KzgWork w) {
+  uint64_t lane = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (lane >= 2 * n) return;
+  const uint8_t *src = lane < n ? cs + 48 * lane : proofs + 48 * (lane - n);
+  g1a p;
+  bool ok = g1_decompress(p, src) == 0;
+  if (ok && !p.inf) {
+    uint8_t be[32];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      uint64_t limb = BLS_ORDER[3 - i];
+#pragma unroll
+      for (int j = 0; j < 8; j++) be[8 * i + j] = (uint8_t)(limb >> (56 - 8 * j));
+    }
+    g1j t;
+    g1j_mul_be(t, p, be, 32);
+    ok = g1j_is_inf(t);
+  }
+  g1j out;
+  if (!ok) {
+    atomicOr(w.fail, 1);
+    g1j_set_inf(out); // harmless placeholder; the call already failed
+  } else {
+    g1j_from_aff(out, p);
+  }
+  w.pts[lane] = out;
+}
+
+// [k]B for an affine G1 base, 32-byte big-endian scalar, mixed adds
+__device__ inline void g1_mul_be32_aff(g1j &r, const g1a &base,
+                                       const uint8_t *be) {
+  g1j acc;
+  g1j_set_inf(acc);
+  for (int i = 0; i < 32; i++) {
+    uint8_t byte = be[i];
+    for (int b = 7; b >= 0; b--) {
+      g1j_dbl(acc, acc);
+      if ((byte >> b) & 1) g1j_add_aff(acc, acc, base);
+    }
+  }
+  r = acc;
+}
+
+// the 3n+1 independent scalar multiplications, one lane each, four
+// role-contiguous classes: r^i pi_i | (r^i z_i) pi_i | r^i C_i | the
+// single folded -(sum r^i y_i) G1. At 1-6 blobs the serial 255-bit chain
+// is the latency, so no lane carries more than one chain.
+__global__ __launch_bounds__(64, 1) void k_kzg_mults(uint64_t n, KzgWork w) {
+  uint64_t lane = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (lane > 3 * n) return;
+  if (*w.fail) return;
+  g1a base;
+  const uint8_t *k;
+  if (lane == 3 * n) {
+    g1_gen(base);
+    k = w.sc + 32 * (2 * n);
+  } else {
+    uint64_t cls = lane / n, i = lane % n;
+    const g1j &src = cls == 2 ? w.pts[i] : w.pts[n + i];
+    base.inf = g1j_is_inf(src) ? 1 : 0;
+    base.x = src.x; // z == 1: affine coordinates
+    base.y = src.y;
+    k = w.sc + 32 * (cls == 1 ? n + i : i);
+  }
+  g1j out;
+  if (base.inf)
+    g1j_set_inf(out);
+  else
+    g1_mul_be32_aff(out, base, k);
+  w.terms[lane] = out;
+}
+
+// two-stage Jacobian G1 sum (k_bls_reduce_sig's shape)
+__global__ __launch_bounds__(256) void k_kzg_reduce_g1(
+    const g1j *__restrict__ in, uint64_t n, g1j *__restrict__ out,
+    const int *__restrict__ fail) {
+  __shared__ g1j lds[256];
+  if (*fail) return;
+  uint64_t per = (n + gridDim.x - 1) / gridDim.x;
+  uint64_t lo = (uint64_t)blockIdx.x * per;
+  uint64_t hi = lo + per < n ? lo + per : n;
+  g1j local;
+  g1j_set_inf(local);
+  for (uint64_t i = lo + threadIdx.x; i < hi; i += 256)
+    g1j_add(local, local, in[i]);
+  lds[threadIdx.x] = local;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+      g1j t;
+      g1j_add(t, lds[threadIdx.x], lds[threadIdx.x + s]);
+      lds[threadIdx.x] = t;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[blockIdx.x] = lds[0];
+}
+
+// the pairing check, one wave (k_bls_finish's shape). miller_w returns one
+// for an infinity argument, which covers all-infinity batches.
+__global__ __launch_bounds__(64) void k_kzg_finish(KzgWork w,
+                                                   const g2j *__restrict__ g2) {
+  __shared__ fp12m sh[7];
+  __shared__ f12w_ws ws;
+  __shared__ miller_ws mws;
+  int lane = threadIdx.x;
+  if (*w.fail) {
+    if (lane == 0) *w.verdict = 0;
+    return;
+  }
+  miller_w(sh[0], w.sums[0], g2[0], ws, mws, lane);
+  f12w_sync();
+  miller_w(sh[1], w.sums[1], g2[1], ws, mws, lane);
+  f12w_sync();
+  f12_mul_w(sh[1], sh[0], sh[1], ws, lane);
+  final_exp_w(sh[2], sh[1], &sh[3], ws, lane);
+  if (lane == 0) *w.verdict = f12_is_one(sh[2]) ? 1 : 0;
+}
+
+// setup validation: [tau]G2 must decode, be in the subgroup, not infinity
+__global__ void k_kzg_setup(const uint8_t *__restrict__ tau96,
+                            g2j *__restrict__ out, int *__restrict__ fail) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  g2a t;
+  if (g2_decompress(t, tau96) != 0 || t.inf || !g2_in_subgroup(t)) {
+    *fail = 1;
+    return;
+  }
+  *fail = 0;
+  out[0].x = t.x;
+  fp2_neg(out[0].y, t.y);
+  fp2_one(out[0].z);
+  FP_LOAD_C(out[1].x.c0, BLS_G2X_C0);
+  FP_LOAD_C(out[1].x.c1, BLS_G2X_C1);
+  FP_LOAD_C(out[1].y.c0, BLS_G2Y_C0);
+  FP_LOAD_C(out[1].y.c1, BLS_G2Y_C1);
+  fp2_one(out[1].z);
+}
+
+// ------------------------------------------------------------------- host
+
+int kzg_layout(m3x_ctx *ctx, uint64_t n, KzgWork &w) {
+  uint64_t bytes = 0;
+  auto align = [](uint64_t x) { return (x + 255) & ~255ull; };
+  uint64_t off_zs = bytes; bytes += align(n * 32);
+  uint64_t off_ys = bytes; bytes += align(n * 32);
+  uint64_t off_tr = bytes; bytes += align(32 + 160 * n);
+  uint64_t off_sc = bytes; bytes += align((2 * n + 1) * 32);
+  uint64_t off_r = bytes; bytes += 256;
+  uint64_t off_pts = bytes; bytes += align(2 * n * sizeof(g1j));
+  uint64_t off_terms = bytes; bytes += align((3 * n + 1) * sizeof(g1j));
+  uint64_t off_stage = bytes; bytes += align(512 * sizeof(g1j));
+  uint64_t off_sums = bytes; bytes += align(2 * sizeof(g1j));
+  uint64_t off_fail = bytes; bytes += 256;
+  uint64_t off_v = bytes; bytes += 256;
+  int rc = m3x::ensure_scratch(ctx, &ctx->scratch_a, &ctx->scratch_a_bytes,
+                               bytes);
+  if (rc != M3X_OK) return rc;
+  uint8_t *base = ctx->scratch_a;
+  w.zs = base + off_zs;
+  w.ys = base + off_ys;
+  w.tr = base + off_tr;
+  w.sc = base + off_sc;
+  w.r_out = base + off_r;
+  w.pts = reinterpret_cast<g1j *>(base + off_pts);
+  w.terms = reinterpret_cast<g1j *>(base + off_terms);
+  w.stage = reinterpret_cast<g1j *>(base + off_stage);
+  w.sums = reinterpret_cast<g1j *>(base + off_sums);
+  w.fail = reinterpret_cast<int *>(base + off_fail);
+  w.verdict = reinterpret_cast<int *>(base + off_v);
+  return M3X_OK;
+}
+
+// challenge (stream2) + evaluation; zs_dev != nullptr supplies explicit z
+int launch_challenge_eval(m3x_ctx *ctx, const KzgWork &w,
+                          const uint8_t *blobs_dev, const uint8_t *cs_dev,
+                          const uint8_t *zs_dev, uint64_t n) {
+  if (zs_dev) {
+    M3X_HIP_CHECK(hipMemcpyAsync(w.zs, zs_dev, n * 32,
+                                 hipMemcpyDeviceToDevice, ctx->stream));
+  } else {
+    m3x::time_begin_s(ctx, M3X_K_KZG_CHALLENGE, ctx->stream2);
+    hipLaunchKernelGGL(k_kzg_challenge, dim3((uint32_t)((n + 63) / 64)),
+                       dim3(64), 0, ctx->stream2, blobs_dev, cs_dev, n, w);
+    m3x::time_end_s(ctx, M3X_K_KZG_CHALLENGE, ctx->stream2);
+    M3X_HIP_CHECK(hipEventRecord(ctx->ev_s2, ctx->stream2));
+    M3X_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->ev_s2, 0));
+  }
+  m3x::time_begin(ctx, M3X_K_KZG_EVAL);
+  hipLaunchKernelGGL(k_kzg_eval, dim3((uint32_t)n), dim3(256), 0, ctx->stream,
+                     blobs_dev, n, w);
+  m3x::time_end(ctx, M3X_K_KZG_EVAL);
+  return M3X_OK;
+}
+
+// blobs_dev != nullptr: blob batch (z, y computed on the device);
+// otherwise zs_dev/ys_dev hold the caller's z and y
+int run_kzg(m3x_ctx *ctx, m3x_kzg *kzg, const uint8_t *blobs_dev,
+            const uint8_t *cs_dev, const uint8_t *zs_dev,
+            const uint8_t *ys_dev, const uint8_t *proofs_dev, uint64_t n,
+            int32_t *out) {
+  KzgWork w;
+  int rc = kzg_layout(ctx, n, w);
+  if (rc != M3X_OK) return rc;
+  M3X_HIP_CHECK(hipMemsetAsync(w.fail, 0, 4, ctx->stream));
+  uint32_t blocks2 = (uint32_t)((2 * n + 63) / 64);
+  // point validation does not depend on z: it runs on the main stream
+  // while the serial challenge hash runs on stream2
+  if (blobs_dev) {
+    m3x::time_begin_s(ctx, M3X_K_KZG_CHALLENGE, ctx->stream2);
+    hipLaunchKernelGGL(k_kzg_challenge, dim3((uint32_t)((n + 63) / 64)),
+                       dim3(64), 0, ctx->stream2, blobs_dev, cs_dev, n, w);
+    m3x::time_end_s(ctx, M3X_K_KZG_CHALLENGE, ctx->stream2);
+    M3X_HIP_CHECK(hipEventRecord(ctx->ev_s2, ctx->stream2));
+  } else {
+    M3X_HIP_CHECK(hipMemcpyAsync(w.zs, zs_dev, n * 32,
+                                 hipMemcpyDeviceToDevice, ctx->stream));
+    M3X_HIP_CHECK(hipMemcpyAsync(w.ys, ys_dev, n * 32,
+                                 hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  m3x::time_begin(ctx, M3X_K_KZG_DECOMP);
+  hipLaunchKernelGGL(k_kzg_decomp, dim3(blocks2), dim3(64), 0, ctx->stream,
+                     cs_dev, proofs_dev, n, w);
+  m3x::time_end(ctx, M3X_K_KZG_DECOMP);
+  if (blobs_dev) {
+    M3X_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->ev_s2, 0));
+    m3x::time_begin(ctx, M3X_K_KZG_EVAL);
+    hipLaunchKernelGGL(k_kzg_eval, dim3((uint32_t)n), dim3(256), 0,
+                       ctx->stream, blobs_dev, n, w);
+    m3x::time_end(ctx, M3X_K_KZG_EVAL);
+  }
+  m3x::time_begin(ctx, M3X_K_KZG_BATCH_R);
+  hipLaunchKernelGGL(k_kzg_batch_r, dim3(1), dim3(256), 0, ctx->stream,
+                     cs_dev, proofs_dev, n, w);
+  m3x::time_end(ctx, M3X_K_KZG_BATCH_R);
+  m3x::time_begin(ctx, M3X_K_KZG_MULTS);
+  hipLaunchKernelGGL(k_kzg_mults, dim3((uint32_t)((3 * n + 1 + 63) / 64)),
+                     dim3(64), 0, ctx->stream, n, w);
+  m3x::time_end(ctx, M3X_K_KZG_MULTS);
+  m3x::time_begin(ctx, M3X_K_KZG_REDUCE);
+  {
+    uint64_t na = n, nb = 2 * n + 1;
+    uint32_t ra = (uint32_t)((na + 255) / 256), rb = (uint32_t)((nb + 255) / 256);
+    if (ra > 256) ra = 256;
+    if (rb > 256) rb = 256;
+    hipLaunchKernelGGL(k_kzg_reduce_g1, dim3(ra), dim3(256), 0, ctx->stream,
+                       w.terms, na, w.stage, w.fail);
+    hipLaunchKernelGGL(k_kzg_reduce_g1, dim3(1), dim3(256), 0, ctx->stream,
+                       w.stage, (uint64_t)ra, w.sums, w.fail);
+    hipLaunchKernelGGL(k_kzg_reduce_g1, dim3(rb), dim3(256), 0, ctx->stream,
+                       w.terms + n, nb, w.stage + 256, w.fail);
+    hipLaunchKernelGGL(k_kzg_reduce_g1, dim3(1), dim3(256), 0, ctx->stream,
+                       w.stage + 256, (uint64_t)rb, w.sums + 1, w.fail);
+  }
+  m3x::time_end(ctx, M3X_K_KZG_REDUCE);
+  m3x::time_begin(ctx, M3X_K_KZG_FINISH);
+  hipLaunchKernelGGL(k_kzg_finish, dim3(1), dim3(64), 0, ctx->stream, w,
+                     kzg->g2);
+  m3x::time_end(ctx, M3X_K_KZG_FINISH);
+  int32_t verdict = 0, fail = 1;
+  M3X_HIP_CHECK(hipMemcpyAsync(&verdict, w.verdict, 4, hipMemcpyDeviceToHost,
+                               ctx->stream));
+  M3X_HIP_CHECK(
+      hipMemcpyAsync(&fail, w.fail, 4, hipMemcpyDeviceToHost, ctx->stream));
+  M3X_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  M3X_HIP_CHECK(hipStreamSynchronize(ctx->stream2));
+  if (fail) return M3X_ERR_ENCODING;
+  *out = verdict;
+  return M3X_OK;
+}
+
+// upload helper: device copy of a host buffer (nullptr on failure)
+uint8_t *dev_copy(const uint8_t *host, uint64_t bytes) {
+  uint8_t *d = nullptr;
+  if (hipMalloc(&d, bytes ? bytes : 4) != hipSuccess) return nullptr;
+  if (bytes && hipMemcpy(d, host, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(d);
+    return nullptr;
+  }
+  return d;
+}
+
+bool kzg_args_ok(m3x_ctx *ctx, m3x_kzg *kzg, uint64_t n) {
+  return ctx && kzg && kzg->g2 && kzg->device == ctx->device &&
+         n <= KZG_MAX_BATCH;
+}
+
+} // namespace
+
+extern "C" {
+
+int32_t m3x_kzg_create(m3x_ctx *ctx, const uint8_t g2_tau[96],
+                       m3x_kzg **out) {
+  if (!ctx || !g2_tau || !out) return M3X_ERR_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  M3X_HIP_CHECK(hipSetDevice(ctx->device));
+  g2j *g2 = nullptr;
+  uint8_t *tau_d = nullptr;
+  int *fail_d = nullptr;
+  int fail = 1;
+  int32_t rc = M3X_ERR_HIP;
+  if (hipMalloc(&g2, 2 * sizeof(g2j)) != hipSuccess) goto out;
+  if (hipMalloc(&tau_d, 96) != hipSuccess) goto out;
+  if (hipMalloc(&fail_d, 4) != hipSuccess) goto out;
+  if (hipMemcpyAsync(tau_d, g2_tau, 96, hipMemcpyHostToDevice, ctx->stream) !=
+      hipSuccess)
+    goto out;
+  hipLaunchKernelGGL(k_kzg_setup, dim3(1), dim3(1), 0, ctx->stream, tau_d, g2,
+                     fail_d);
+  if (hipMemcpyAsync(&fail, fail_d, 4, hipMemcpyDeviceToHost, ctx->stream) !=
+      hipSuccess)
+    goto out;
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) goto out;
+  rc = fail ? M3X_ERR_ENCODING : M3X_OK;
+out:
+  if (tau_d) (void)hipFree(tau_d);
+  if (fail_d) (void)hipFree(fail_d);
+  if (rc != M3X_OK) {
+    if (g2) (void)hipFree(g2);
+    return rc;
+  }
+  auto *k = new m3x_kzg();
+  k->device = ctx->device;
+  k->g2 = g2;
+  *out = k;
+  return M3X_OK;
+}
+
+void m3x_kzg_destroy(m3x_kzg *kzg) {
+  if (!kzg) return;
+  if (kzg->g2 && hipSetDevice(kzg->device) == hipSuccess)
+    (void)hipFree(kzg->g2);
+  delete kzg;
+}
+
+int32_t m3x_kzg_verify_proof_batch(m3x_ctx *ctx, m3x_kzg *kzg,
+                                   const uint8_t *cs, const uint8_t *zs,
+                                   const uint8_t *ys, const uint8_t *proofs,
+                                   uint64_t n) {
+  if (!kzg_args_ok(ctx, kzg, n)) return M3X_ERR_ARG;
+  if (n == 0) return 1;
+  if (!cs || !zs || !ys || !proofs) return M3X_ERR_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  M3X_HIP_CHECK(hipSetDevice(ctx->device));
+  uint8_t *cs_d = dev_copy(cs, n * 48), *zs_d = dev_copy(zs, n * 32),
+          *ys_d = dev_copy(ys, n * 32), *pr_d = dev_copy(proofs, n * 48);
+  int32_t rc = M3X_ERR_HIP, verdict = 0;
+  if (cs_d && zs_d && ys_d && pr_d) {
+    rc = run_kzg(ctx, kzg, nullptr, cs_d, zs_d, ys_d, pr_d, n, &verdict);
+    if (rc == M3X_OK) rc = verdict;
+  }
+  if (cs_d) (void)hipFree(cs_d);
+  if (zs_d) (void)hipFree(zs_d);
+  if (ys_d) (void)hipFree(ys_d);
+  if (pr_d) (void)hipFree(pr_d);
+  return rc;
+}
+
+int32_t m3x_kzg_verify_proof(m3x_ctx *ctx, m3x_kzg *kzg, const uint8_t c[48],
+                             const uint8_t z[32], const uint8_t y[32],
+                             const uint8_t proof[48]) {
+  return m3x_kzg_verify_proof_batch(ctx, kzg, c, z, y, proof, 1);
+}
+
+int32_t m3x_kzg_verify_blob_proof_batch_dev(m3x_ctx *ctx, m3x_kzg *kzg,
+                                            const void *blobs_dev,
+                                            const void *cs_dev,
+                                            const void *proofs_dev,
+                                            uint64_t n) {
+  if (!kzg_args_ok(ctx, kzg, n)) return M3X_ERR_ARG;
+  if (n == 0) return 1;
+  if (!blobs_dev || !cs_dev || !proofs_dev) return M3X_ERR_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  M3X_HIP_CHECK(hipSetDevice(ctx->device));
+  int32_t verdict = 0;
+  int rc = run_kzg(ctx, kzg, (const uint8_t *)blobs_dev,
+                   (const uint8_t *)cs_dev, nullptr, nullptr,
+                   (const uint8_t *)proofs_dev, n, &verdict);
+  return rc == M3X_OK ? verdict : rc;
+}
+
+int32_t m3x_kzg_verify_blob_proof_batch(m3x_ctx *ctx, m3x_kzg *kzg,
+                                        const uint8_t *blobs,
+                                        const uint8_t *cs,
+                                        const uint8_t *proofs, uint64_t n) {
+  if (!kzg_args_ok(ctx, kzg, n)) return M3X_ERR_ARG;
+  if (n == 0) return 1;
+  if (!blobs || !cs || !proofs) return M3X_ERR_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  M3X_HIP_CHECK(hipSetDevice(ctx->device));
+  uint8_t *bl_d = dev_copy(blobs, n * KZG_BLOB_BYTES),
+          *cs_d = dev_copy(cs, n * 48), *pr_d = dev_copy(proofs, n * 48);
+  int32_t rc = M3X_ERR_HIP;
+  if (bl_d && cs_d && pr_d)
+    rc = m3x_kzg_verify_blob_proof_batch_dev(ctx, kzg, bl_d, cs_d, pr_d, n);
+  if (bl_d) (void)hipFree(bl_d);
+  if (cs_d) (void)hipFree(cs_d);
+  if (pr_d) (void)hipFree(pr_d);
+  return rc;
+}
+
+int32_t m3x_kzg_blob_challenge_eval(m3x_ctx *ctx, const uint8_t *blobs,
+                                    const uint8_t *cs, const uint8_t *zs_in,
+                                    uint64_t n, uint8_t *out_z,
+                                    uint8_t *out_y) {
+  if (!ctx || !blobs || !cs || !out_z || !out_y || n == 0 ||
+      n > KZG_MAX_BATCH)
+    return M3X_ERR_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  M3X_HIP_CHECK(hipSetDevice(ctx->device));
+  KzgWork w;
+  int32_t rc = kzg_layout(ctx, n, w);
+  if (rc != M3X_OK) return rc;
+  uint8_t *bl_d = dev_copy(blobs, n * KZG_BLOB_BYTES),
+          *cs_d = dev_copy(cs, n * 48),
+          *zs_d = zs_in ? dev_copy(zs_in, n * 32) : nullptr;
+  int fail = 1;
+  rc = M3X_ERR_HIP;
+  if (!bl_d || !cs_d || (zs_in && !zs_d)) goto out;
+  if (hipMemsetAsync(w.fail, 0, 4, ctx->stream) != hipSuccess) goto out;
+  if (launch_challenge_eval(ctx, w, bl_d, cs_d, zs_d, n) != M3X_OK) goto out;
+  if (hipMemcpyAsync(out_z, w.zs, n * 32, hipMemcpyDeviceToHost,
+                     ctx->stream) != hipSuccess)
+    goto out;
+  if (hipMemcpyAsync(out_y, w.ys, n * 32, hipMemcpyDeviceToHost,
+                     ctx->stream) != hipSuccess)
+    goto out;
+  if (hipMemcpyAsync(&fail, w.fail, 4, hipMemcpyDeviceToHost, ctx->stream) !=
+      hipSuccess)
+    goto out;
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) goto out;
+  rc = fail ? M3X_ERR_ENCODING : M3X_OK;
+out:
+  (void)hipStreamSynchronize(ctx->stream2);
+  (void)hipStreamSynchronize(ctx->stream);
+  if (bl_d) (void)hipFree(bl_d);
+  if (cs_d) (void)hipFree(cs_d);
+  if (zs_d) (void)hipFree(zs_d);
+  return rc;
+}
+
+int32_t m3x_kzg_batch_challenge_test(m3x_ctx *ctx, const uint8_t *cs,
+                                     const uint8_t *zs, const uint8_t *ys,
+                                     const uint8_t *proofs, uint64_t n,
+                                     uint8_t out_r[32]) {
+  if (!ctx || !cs || !zs || !ys || !proofs || !out_r || n == 0 ||
+      n > KZG_MAX_BATCH)
+    return M3X_ERR_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  M3X_HIP_CHECK(hipSetDevice(ctx->device));
+  KzgWork w;
+  int32_t rc = kzg_layout(ctx, n, w);
+  if (rc != M3X_OK) return rc;
+  uint8_t *cs_d = dev_copy(cs, n * 48), *pr_d = dev_copy(proofs, n * 48);
+  int fail = 1;
+  rc = M3X_ERR_HIP;
+  if (!cs_d || !pr_d) goto out;
+  if (hipMemsetAsync(w.fail, 0, 4, ctx->stream) != hipSuccess) goto out;
+  if (hipMemcpyAsync(w.zs, zs, n * 32, hipMemcpyHostToDevice, ctx->stream) !=
+      hipSuccess)
+    goto out;
+  if (hipMemcpyAsync(w.ys, ys, n * 32, hipMemcpyHostToDevice, ctx->stream) !=
+      hipSuccess)
+    goto out;
+  hipLaunchKernelGGL(k_kzg_batch_r, dim3(1), dim3(256), 0, ctx->stream, cs_d,
+                     pr_d, n, w);
+  if (hipMemcpyAsync(out_r, w.r_out, 32, hipMemcpyDeviceToHost,
+                     ctx->stream) != hipSuccess)
+    goto out;
+  if (hipMemcpyAsync(&fail, w.fail, 4, hipMemcpyDeviceToHost, ctx->stream) !=
+      hipSuccess)
+    goto out;
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) goto out;
+  rc = fail ? M3X_ERR_ENCODING : M3X_OK;
+out:
+  (void)hipStreamSynchronize(ctx->stream);
+  if (cs_d) (void)hipFree(cs_d);
+  if (pr_d) (void)hipFree(pr_d);
+  return rc;
+}
+
+} // extern "C"

@@ -1,0 +1,195 @@
+"""KZG blob proof verification on the GPU — the verification half of the
+reference's `Kzg` wrapper (crypto/kzg/src/lib.rs:62-167): verify_kzg_proof,
+verify_blob_kzg_proof and verify_blob_kzg_proof_batch.
+
+Verification needs one trusted-setup point, [tau]G2 (entry 1 of the
+ceremony's g2_monomial list, 96 bytes compressed). All byte strings are the
+spec's big-endian wire forms. Every method returns a bool: a proof that
+does not verify is False; malformed input (bad point encoding, a point
+outside the subgroup, a scalar >= the field modulus, wrong lengths)
+raises KzgError, the analogue of the reference's Error::Kzg /
+InconsistentArrayLength. No CPU fallback (package rule)."""
+import ctypes
+from typing import Optional, Sequence
+
+from . import _native
+
+BYTES_PER_FIELD_ELEMENT = 32
+FIELD_ELEMENTS_PER_BLOB = 4096
+BYTES_PER_BLOB = BYTES_PER_FIELD_ELEMENT * FIELD_ELEMENTS_PER_BLOB
+BYTES_PER_COMMITMENT = 48
+BYTES_PER_PROOF = 48
+BYTES_PER_G2_POINT = 96
+BLS_MODULUS = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
+
+_ERR_ENCODING = -4
+
+
+class KzgError(ValueError):
+    """Malformed input (the c_kzg::Error / InconsistentArrayLength analogue)."""
+
+
+def _check_len(name, b, want):
+    if not isinstance(b, (bytes, bytearray)) or len(b) != want:
+        got = len(b) if hasattr(b, "__len__") else type(b).__name__
+        raise KzgError(f"{name}: expected {want} bytes, got {got}")
+    return bytes(b)
+
+
+def _verdict(rc, what):
+    if rc == 1:
+        return True
+    if rc == 0:
+        return False
+    if rc == _ERR_ENCODING:
+        raise KzgError(f"{what}: malformed point or non-canonical field element")
+    raise RuntimeError(f"{what} failed (rc={rc})")
+
+
+class Kzg:
+    """Verification-side trusted setup, bound to one GPU context."""
+
+    def __init__(self, g2_tau: bytes, ctx: Optional[_native.Ctx] = None):
+        g2_tau = _check_len("g2_tau", g2_tau, BYTES_PER_G2_POINT)
+        self._ctx = ctx or _native.default_ctx()
+        self._lib = _native.load()
+        self._h = ctypes.c_void_p()
+        rc = self._lib.m3x_kzg_create(
+            self._ctx.handle, g2_tau, ctypes.byref(self._h)
+        )
+        if rc == _ERR_ENCODING:
+            raise KzgError("g2_tau is not a valid non-infinity G2 subgroup point")
+        if rc != 0:
+            raise RuntimeError(f"m3x_kzg_create failed (rc={rc})")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.m3x_kzg_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- lib.rs:152-167 ----
+    def verify_kzg_proof(self, commitment: bytes, z: bytes, y: bytes,
+                         proof: bytes) -> bool:
+        commitment = _check_len("commitment", commitment, BYTES_PER_COMMITMENT)
+        z = _check_len("z", z, BYTES_PER_FIELD_ELEMENT)
+        y = _check_len("y", y, BYTES_PER_FIELD_ELEMENT)
+        proof = _check_len("proof", proof, BYTES_PER_PROOF)
+        rc = self._lib.m3x_kzg_verify_proof(
+            self._ctx.handle, self._h, commitment, z, y, proof
+        )
+        return _verdict(rc, "verify_kzg_proof")
+
+    def verify_kzg_proof_batch(self, commitments: Sequence[bytes],
+                               zs: Sequence[bytes], ys: Sequence[bytes],
+                               proofs: Sequence[bytes]) -> bool:
+        n = len(commitments)
+        if not (n == len(zs) == len(ys) == len(proofs)):
+            raise KzgError(
+                "inconsistent array length: "
+                f"{n} commitments, {len(zs)} zs, {len(ys)} ys, {len(proofs)} proofs"
+            )
+        if n == 0:
+            return True
+        cs = b"".join(_check_len("commitment", c, BYTES_PER_COMMITMENT) for c in commitments)
+        zb = b"".join(_check_len("z", z, BYTES_PER_FIELD_ELEMENT) for z in zs)
+        yb = b"".join(_check_len("y", y, BYTES_PER_FIELD_ELEMENT) for y in ys)
+        ps = b"".join(_check_len("proof", p, BYTES_PER_PROOF) for p in proofs)
+        rc = self._lib.m3x_kzg_verify_proof_batch(
+            self._ctx.handle, self._h, cs, zb, yb, ps, n
+        )
+        return _verdict(rc, "verify_kzg_proof_batch")
+
+    # ---- lib.rs:83-103 ----
+    def verify_blob_kzg_proof(self, blob: bytes, commitment: bytes,
+                              proof: bytes) -> bool:
+        return self.verify_blob_kzg_proof_batch([blob], [commitment], [proof])
+
+    # ---- lib.rs:105-132 ----
+    def verify_blob_kzg_proof_batch(self, blobs: Sequence[bytes],
+                                    commitments: Sequence[bytes],
+                                    proofs: Sequence[bytes]) -> bool:
+        n = len(blobs)
+        if not (n == len(commitments) == len(proofs)):
+            raise KzgError(
+                "inconsistent array length: "
+                f"{n} blobs, {len(commitments)} commitments, {len(proofs)} proofs"
+            )
+        if n == 0:
+            return True
+        bl = b"".join(_check_len("blob", b, BYTES_PER_BLOB) for b in blobs)
+        cs = b"".join(_check_len("commitment", c, BYTES_PER_COMMITMENT) for c in commitments)
+        ps = b"".join(_check_len("proof", p, BYTES_PER_PROOF) for p in proofs)
+        rc = self._lib.m3x_kzg_verify_blob_proof_batch(
+            self._ctx.handle, self._h, bl, cs, ps, n
+        )
+        return _verdict(rc, "verify_blob_kzg_proof_batch")
+
+    def verify_blob_kzg_proof_batch_dev(self, blobs_dev, commitments_dev,
+                                        proofs_dev, n: int) -> bool:
+        """Same check over inputs already resident in device memory
+        (Ctx.upload): blobs n*131072, commitments n*48, proofs n*48."""
+        rc = self._lib.m3x_kzg_verify_blob_proof_batch_dev(
+            self._ctx.handle, self._h, blobs_dev, commitments_dev, proofs_dev, n
+        )
+        return _verdict(rc, "verify_blob_kzg_proof_batch_dev")
+
+
+# ---- test/introspection seams (parity tests; not on the import path) ----
+def blob_challenge_eval(blobs: Sequence[bytes], commitments: Sequence[bytes],
+                        zs: Optional[Sequence[bytes]] = None,
+                        ctx: Optional[_native.Ctx] = None):
+    """[(z_i, y_i)]: z_i = compute_challenge(blob_i, commitment_i), or
+    zs[i] when given; y_i = the blob polynomial evaluated at z_i."""
+    n = len(blobs)
+    if n != len(commitments) or (zs is not None and n != len(zs)) or n == 0:
+        raise KzgError("inconsistent array length")
+    ctx = ctx or _native.default_ctx()
+    bl = b"".join(_check_len("blob", b, BYTES_PER_BLOB) for b in blobs)
+    cs = b"".join(_check_len("commitment", c, BYTES_PER_COMMITMENT) for c in commitments)
+    zb = None
+    if zs is not None:
+        zb = b"".join(_check_len("z", z, BYTES_PER_FIELD_ELEMENT) for z in zs)
+    out_z = ctypes.create_string_buffer(32 * n)
+    out_y = ctypes.create_string_buffer(32 * n)
+    rc = _native.load().m3x_kzg_blob_challenge_eval(
+        ctx.handle, bl, cs, zb, n, out_z, out_y
+    )
+    if rc == _ERR_ENCODING:
+        raise KzgError("non-canonical field element")
+    if rc != 0:
+        raise RuntimeError(f"m3x_kzg_blob_challenge_eval rc={rc}")
+    return [
+        (out_z.raw[32 * i : 32 * i + 32], out_y.raw[32 * i : 32 * i + 32])
+        for i in range(n)
+    ]
+
+
+def batch_challenge(commitments: Sequence[bytes], zs: Sequence[bytes],
+                    ys: Sequence[bytes], proofs: Sequence[bytes],
+                    ctx: Optional[_native.Ctx] = None) -> bytes:
+    """The verify_kzg_proof_batch Fiat-Shamir challenge r, 32 bytes BE."""
+    n = len(commitments)
+    if not (n == len(zs) == len(ys) == len(proofs)) or n == 0:
+        raise KzgError("inconsistent array length")
+    ctx = ctx or _native.default_ctx()
+    out = ctypes.create_string_buffer(32)
+    rc = _native.load().m3x_kzg_batch_challenge_test(
+        ctx.handle,
+        b"".join(_check_len("commitment", c, 48) for c in commitments),
+        b"".join(_check_len("z", z, 32) for z in zs),
+        b"".join(_check_len("y", y, 32) for y in ys),
+        b"".join(_check_len("proof", p, 48) for p in proofs),
+        n,
+        out,
+    )
+    if rc == _ERR_ENCODING:
+        raise KzgError("non-canonical field element")
+    if rc != 0:
+        raise RuntimeError(f"m3x_kzg_batch_challenge_test rc={rc}")
+    return out.raw

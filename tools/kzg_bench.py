@@ -1,0 +1,117 @@
+#!/usr/bin/env python3
+"""Stand-alone timing of KZG blob proof batch verification (not bench.py).
+
+For n = 1, 6 and 192 blobs: end-to-end verify_blob_kzg_proof_batch time
+over device-resident inputs (host clock around calls that end in a stream
+synchronise; min / median / max over --reps after --warmup) -> blobs/s, and
+in a separate pass the per-kernel HIP-event times (with timing on, each
+kernel is synchronised, so the stream overlap is off and the kernel times
+do not sum to the end-to-end time). Prints one JSON line per n.
+
+Inputs are three distinct seed-derived blobs cycled to n, with commitments
+and proofs made under the insecure test setup of
+tests/golden/kzg_fixtures.json (CPU oracle: test infrastructure). Needs a
+GPU; there is no fallback. No CPU KZG implementation exists in this tree,
+so no CPU ratio is computed."""
+import argparse
+import ctypes
+import hashlib
+import json
+import statistics
+import subprocess
+import sys
+import time
+from pathlib import Path
+
+REPO = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(REPO))
+sys.path.insert(0, str(REPO / "tests"))
+sys.path.insert(0, str(REPO / "tests" / "golden"))
+
+
+def make_triples(g2_seed):
+    import gen_bls_fixtures as G
+    import kzg_ref as K
+
+    subprocess.run(["make", "-s", "-C", str(REPO / "oracle")], check=True)
+    oracle = ctypes.CDLL(str(REPO / "oracle" / "liboracle.so"))
+    tau = int.from_bytes(hashlib.sha256(g2_seed.encode()).digest(), "big") % K.R
+
+    def g1_mul(k):
+        k %= K.R
+        if k == 0:
+            return K.G1_POINT_AT_INFINITY
+        out = ctypes.create_string_buffer(96)
+        assert oracle.m3x_oracle_bls_g1_mul(
+            G.g1_uncompressed(G.G1G), k.to_bytes(32, "big"), out) == 0
+        raw = out.raw
+        return G.g1_compress(
+            (int.from_bytes(raw[:48], "big"), int.from_bytes(raw[48:], "big")))
+
+    out = []
+    for i in range(3):
+        blob = K.blob_from_seed(b"kzg-bench-%d" % i)
+        poly = K.blob_to_polynomial(blob)
+        p_tau = K.poly_eval_at_secret(poly, tau)
+        c = g1_mul(p_tau)
+        z = K.compute_challenge(blob, c)
+        y = K.evaluate_polynomial_in_evaluation_form(poly, z)
+        q_tau = (p_tau - y) * pow((tau - z) % K.R, -1, K.R) % K.R
+        out.append((blob, c, g1_mul(q_tau)))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--sizes", default="1,6,192")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    args = ap.parse_args()
+
+    from lighthouse_amd import _native, kzg
+
+    fx = json.loads((REPO / "tests" / "golden" / "kzg_fixtures.json").read_text())
+    triples = make_triples(fx["test_setup"]["tau_seed"])
+    ctx = _native.default_ctx()
+    k = kzg.Kzg(bytes.fromhex(fx["test_setup"]["g2_tau"]), ctx=ctx)
+    for n in [int(s) for s in args.sizes.split(",")]:
+        ts = [triples[i % 3] for i in range(n)]
+        blobs_d = ctx.upload(b"".join(t[0] for t in ts))
+        cs_d = ctx.upload(b"".join(t[1] for t in ts))
+        ps_d = ctx.upload(b"".join(t[2] for t in ts))
+        run = lambda: k.verify_blob_kzg_proof_batch_dev(blobs_d, cs_d, ps_d, n)  # noqa: E731
+        for _ in range(args.warmup):
+            assert run() is True
+        times = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            ok = run()
+            times.append(time.perf_counter() - t0)
+            assert ok is True
+        ctx.timing_enable(True)
+        kreps = max(3, args.reps // 4)
+        for _ in range(kreps):
+            assert run() is True
+        kernels = {
+            name: round(ms / kreps, 4)
+            for name, (ms, launches) in ctx.kernel_times().items()
+            if name.startswith("kzg_") and launches
+        }
+        ctx.timing_enable(False)
+        for p in (blobs_d, cs_d, ps_d):
+            ctx.free(p)
+        med = statistics.median(times)
+        print(json.dumps({
+            "n_blobs": n,
+            "reps": args.reps,
+            "ms_min": round(min(times) * 1e3, 4),
+            "ms_median": round(med * 1e3, 4),
+            "ms_max": round(max(times) * 1e3, 4),
+            "blobs_per_s_median": round(n / med, 2),
+            "kernel_ms_serialised": kernels,
+        }), flush=True)
+    k.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -52,7 +52,8 @@ int32_t m3x_abi_version(void);
  * accumulators; kernel ids are the M3X_K_* slots (0 leaves, 1 reduce,
  * 2 finalize, 3 bls_prepare, 4 bls_h2c, 5 bls_miller, 6 bls_reduce,
  * 7 bls_finish, 8 bls_agg, 9 kzg_challenge, 10 kzg_decomp, 11 kzg_eval,
- * 12 kzg_batch_r, 13 kzg_mults, 14 kzg_reduce, 15 kzg_finish). */
+ * 12 kzg_batch_r, 13 kzg_mults, 14 kzg_reduce, 15 kzg_finish,
+ * 16 kzgp_quotient, 17 kzgp_msm, 18 kzgp_finish). */
 int32_t m3x_timing_enable(m3x_ctx *ctx, int32_t on);
 int32_t m3x_kernel_ms(m3x_ctx *ctx, int32_t kernel_id, double *ms,
                       uint64_t *launches);
@@ -229,6 +230,55 @@ int32_t m3x_kzg_verify_blob_proof_batch_dev(m3x_ctx *ctx, m3x_kzg *kzg,
                                             const void *cs_dev,
                                             const void *proofs_dev,
                                             uint64_t n);
+
+/* ---- KZG commitments and proofs ("KZG prover"; crypto/kzg/src/lib.rs) ----
+ *
+ * The producing half of the Kzg wrapper, on the m3x_kzg handle above. Every
+ * result is sum_i s_i * L_i over the setup's 4096 Lagrange points: a
+ * fixed-base multi-scalar multiplication served from a precomputed table of
+ * [d * 16^j] L_i (d = 1..8, j = 0..63; about 200 MB of device memory per
+ * handle). Calls return 0 on success (n == 0 included), M3X_ERR_ENCODING
+ * for a non-canonical blob element or z, or a bad commitment, and
+ * M3X_ERR_ARG on a handle that has no Lagrange basis loaded. */
+
+/* Kzg::new_from_trusted_setup (lib.rs:62-70), the g1_lagrange part: 4096 x
+ * 48B compressed points in the ceremony file's order (the bit-reversal
+ * permutation is applied inside, as c-kzg does). Every point is validated
+ * on the device (decodes, in the subgroup, not infinity; else
+ * M3X_ERR_ENCODING and the handle stays verification-only), then the table
+ * is built once and lives as long as the handle. One load per handle. */
+int32_t m3x_kzgp_load_g1_lagrange(m3x_ctx *ctx, m3x_kzg *kzg,
+                                  const uint8_t *g1_lagrange /* 4096*48 */);
+
+/* Kzg::blob_to_kzg_commitment (lib.rs:134-139), n blobs in one call:
+ * blobs n*131072 -> out n*48 */
+int32_t m3x_kzgp_blob_to_commitment(m3x_ctx *ctx, m3x_kzg *kzg,
+                                    const uint8_t *blobs, uint64_t n,
+                                    uint8_t *out);
+/* Kzg::compute_kzg_proof (lib.rs:141-150): blobs n*131072, zs n*32 ->
+ * proofs_out n*48 and ys_out n*32 (y_i = p_i(z_i)); z inside the
+ * evaluation domain takes the spec's in-domain quotient term */
+int32_t m3x_kzgp_compute_proof(m3x_ctx *ctx, m3x_kzg *kzg,
+                               const uint8_t *blobs, const uint8_t *zs,
+                               uint64_t n, uint8_t *proofs_out,
+                               uint8_t *ys_out);
+/* Kzg::compute_blob_kzg_proof (lib.rs:72-81): blobs n*131072, cs n*48
+ * (validated like any KZG point; infinity is valid) -> out n*48 */
+int32_t m3x_kzgp_compute_blob_proof(m3x_ctx *ctx, m3x_kzg *kzg,
+                                    const uint8_t *blobs, const uint8_t *cs,
+                                    uint64_t n, uint8_t *out);
+/* the same three with every input and output in device memory */
+int32_t m3x_kzgp_blob_to_commitment_dev(m3x_ctx *ctx, m3x_kzg *kzg,
+                                        const void *blobs_dev, uint64_t n,
+                                        void *out_dev);
+int32_t m3x_kzgp_compute_proof_dev(m3x_ctx *ctx, m3x_kzg *kzg,
+                                   const void *blobs_dev, const void *zs_dev,
+                                   uint64_t n, void *proofs_out_dev,
+                                   void *ys_out_dev);
+int32_t m3x_kzgp_compute_blob_proof_dev(m3x_ctx *ctx, m3x_kzg *kzg,
+                                        const void *blobs_dev,
+                                        const void *cs_dev, uint64_t n,
+                                        void *out_dev);
 
 /* test/introspection seams (like m3x_bls_h2c_test; not on the hot path).
  * blob_challenge_eval: z_i = compute_challenge(blob_i, c_i) (or zs_in[i]

@@ -253,6 +253,42 @@ def _bind(lib):
              ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint64,
              ctypes.c_char_p],
         ),
+        (
+            "m3x_kzgp_load_g1_lagrange",
+            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p],
+        ),
+        (
+            "m3x_kzgp_blob_to_commitment",
+            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p,
+             ctypes.c_uint64, ctypes.c_char_p],
+        ),
+        (
+            "m3x_kzgp_compute_proof",
+            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p,
+             ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p,
+             ctypes.c_char_p],
+        ),
+        (
+            "m3x_kzgp_compute_blob_proof",
+            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p,
+             ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p],
+        ),
+        (
+            "m3x_kzgp_blob_to_commitment_dev",
+            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+             ctypes.c_uint64, ctypes.c_void_p],
+        ),
+        (
+            "m3x_kzgp_compute_proof_dev",
+            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+             ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+             ctypes.c_void_p],
+        ),
+        (
+            "m3x_kzgp_compute_blob_proof_dev",
+            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+             ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p],
+        ),
     ]:
         try:
             fn = getattr(lib, name)
@@ -355,6 +391,9 @@ class Ctx:
         "kzg_mults",
         "kzg_reduce",
         "kzg_finish",
+        "kzgp_quotient",
+        "kzgp_msm",
+        "kzgp_finish",
     ]
 
     def kernel_times(self):

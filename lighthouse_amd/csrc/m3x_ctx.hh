@@ -22,7 +22,10 @@ enum m3x_kernel_id {
   M3X_K_KZG_MULTS = 13,    // G1 scalar multiplications
   M3X_K_KZG_REDUCE = 14,   // G1 sums
   M3X_K_KZG_FINISH = 15,   // pairing check
-  M3X_K_COUNT = 16
+  M3X_K_KZGP_QUOTIENT = 16, // proof quotient in evaluation form
+  M3X_K_KZGP_MSM = 17,      // fixed-base MSM: table look-ups + block sums
+  M3X_K_KZGP_FINISH = 18,   // last G1 sum + compression
+  M3X_K_COUNT = 19
 };
 
 struct m3x_ctx {

@@ -20,6 +20,10 @@
 // The batch equation is used for n == 1 too (r^0 = 1): it is algebraically
 // the spec's single-proof check and needs no G2 scalar multiplication.
 // Integer VALU workload (no MFMA); Fp/G1/pairing code is bls_device.hh's.
+//
+// The producing half (blob_to_kzg_commitment, compute_kzg_proof,
+// compute_blob_kzg_proof; lib.rs:72-81, 134-150) is the "prover" section
+// further down: a fixed-base G1 MSM over the Lagrange setup points.
 #include "bls_device.hh"
 #include "fr_device.hh"
 #include "m3x_ctx.hh"
@@ -36,6 +40,14 @@ using namespace m3xf;
 struct m3x_kzg {
   int device = 0;
   g2j *g2 = nullptr; // [0] = -[tau]G2, [1] = G2 generator (z = 1)
+  // prover only (m3x_kzgp_load_g1_lagrange): the fixed-base table
+  // T[j][i][d-1] = [d * 2^(4j)] L_i, affine, i in blob (bit-reversed) order
+  struct g1t *table = nullptr;
+};
+
+// affine table entry; no entry is infinity (d * 2^(4j) is never 0 mod r)
+struct g1t {
+  fp x, y;
 };
 
 namespace {
@@ -64,6 +76,20 @@ __device__ __forceinline__ void g1j_set_inf(g1j &p) {
   fp_zero(p.x);
   fp_zero(p.y);
   fp_zero(p.z);
+}
+
+// Jacobian -> 48-byte compressed form, the inverse of g1_decompress: the
+// sign bit follows the same lexicographic rule, infinity is 0xc0 00...
+__device__ inline void g1_compress(uint8_t *out, const g1j &p) {
+  if (g1j_is_inf(p)) {
+    for (int i = 0; i < 48; i++) out[i] = 0;
+    out[0] = 0xC0;
+    return;
+  }
+  g1a a;
+  g1j_to_aff(a, p);
+  fp_to_be48(a.x, out);
+  out[0] |= fp_gt_half(a.y) ? 0xA0 : 0x80;
 }
 
 // "FSBLOBVERIFY_V1_" / "RCKZGBATCH___V1_" as big-endian words / bytes
@@ -285,16 +311,9 @@ __global__ __launch_bounds__(256) void k_kzg_batch_r(
   if (bad) atomicOr(w.fail, 1);
 }
 
-// validate_kzg_g1 for every commitment and proof: decompress (infinity is
-// a valid KZG point, unlike a public key) + subgroup check as in
-// k_bls_pk_decompress. One lane per point.
-__global__ __launch_bounds__(64, 1) void k_kzg_decomp(
-    const uint8_t *__restrict__ cs, const uint8_t *__restrict__ proofs,
-    uint64_t n, KzgWork w) {
-  uint64_t lane = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (lane >= 2 * n) return;
-  const uint8_t *src = lane < n ? cs + 48 * lane : proofs + 48 * (lane - n);
-  g1a p;
+// validate_kzg_g1: decompress (infinity is a valid KZG point, unlike a
+// public key) + subgroup check as in k_bls_pk_decompress
+__device__ inline bool kzg_validate_g1(g1a &p, const uint8_t *src) {
   bool ok = g1_decompress(p, src) == 0;
   if (ok && !p.inf) {
     uint8_t be[32];
@@ -308,6 +327,18 @@ __global__ __launch_bounds__(64, 1) void k_kzg_decomp(
     g1j_mul_be(t, p, be, 32);
     ok = g1j_is_inf(t);
   }
+  return ok;
+}
+
+// validate_kzg_g1 for every commitment and proof. One lane per point.
+__global__ __launch_bounds__(64, 1) void k_kzg_decomp(
+    const uint8_t *__restrict__ cs, const uint8_t *__restrict__ proofs,
+    uint64_t n, KzgWork w) {
+  uint64_t lane = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (lane >= 2 * n) return;
+  const uint8_t *src = lane < n ? cs + 48 * lane : proofs + 48 * (lane - n);
+  g1a p;
+  bool ok = kzg_validate_g1(p, src);
   g1j out;
   if (!ok) {
     atomicOr(w.fail, 1);
@@ -577,6 +608,347 @@ bool kzg_args_ok(m3x_ctx *ctx, m3x_kzg *kzg, uint64_t n) {
          n <= KZG_MAX_BATCH;
 }
 
+// ================================================================= prover
+//
+// blob_to_kzg_commitment / compute_kzg_proof / compute_blob_kzg_proof: a
+// 4096-term G1 multi-scalar multiplication over the fixed Lagrange basis.
+// Fixed basis => no doublings and no buckets at run time: with signed
+// 4-bit digits s = sum_j d_j 16^j, d_j in [-7, 8],
+//   sum_i s_i L_i = sum_{i,j} sign(d_ij) * T[j][i][|d_ij| - 1]
+// is 64 * 4096 table look-ups joined by mixed additions.
+//   k_kzgp_bases     validate the 4096 points, bases[j][i] = [16^j] L_i
+//   k_kzgp_table     d = 1..8 multiples of every base, one shared inversion
+//   k_kzgp_quotient  q_i = (f_i - y)/(w_i - z), with the in-domain term
+//   k_kzgp_msm       16 look-ups per lane, 16384 lanes per blob, block sum
+//   k_kzgp_finish    the last 64 partial sums of a blob + g1_compress
+
+#define KZGP_WINDOWS 64  // 4-bit windows of a 256-bit scalar
+#define KZGP_DIGITS 8    // table multiples d = 1..8
+#define KZGP_PER_LANE 16 // windows (look-ups) per MSM lane
+#define KZGP_BLOCKS (KZG_N * (KZGP_WINDOWS / KZGP_PER_LANE) / 256)
+#define KZGP_TABLE_POINTS ((uint64_t)KZGP_WINDOWS * KZG_N * KZGP_DIGITS)
+
+// one lane per Lagrange point, in blob order: element e of a blob pairs
+// with entry bitrev12(e) of the ceremony file's list
+__global__ __launch_bounds__(64, 1) void k_kzgp_bases(
+    const uint8_t *__restrict__ lagrange, g1j *__restrict__ bases,
+    int *__restrict__ fail) {
+  uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= KZG_N) return;
+  g1a p;
+  bool ok = kzg_validate_g1(p, lagrange + 48 * bitrev_lo(e, 12)) && !p.inf;
+  if (!ok) {
+    atomicOr(fail, 1);
+    g1_gen(p); // placeholder; the load already failed
+  }
+  g1j b;
+  g1j_from_aff(b, p);
+  for (int j = 0; j < KZGP_WINDOWS; j++) {
+    bases[(uint32_t)j * KZG_N + e] = b;
+    for (int k = 0; k < 4; k++) g1j_dbl(b, b);
+  }
+}
+
+// lane (j, i): B, 2B, ..., 8B in Jacobian form, then affine through one
+// inversion of the product of the eight z (Montgomery's trick)
+__global__ __launch_bounds__(64, 1) void k_kzgp_table(
+    const g1j *__restrict__ bases, g1t *__restrict__ table) {
+  uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x;
+  if (lane >= KZGP_WINDOWS * KZG_N) return;
+  g1j m[KZGP_DIGITS];
+  m[0] = bases[lane];
+  g1j_dbl(m[1], m[0]);
+  g1j_add(m[2], m[1], m[0]);
+  g1j_dbl(m[3], m[1]);
+  g1j_add(m[4], m[3], m[0]);
+  g1j_dbl(m[5], m[2]);
+  g1j_add(m[6], m[5], m[0]);
+  g1j_dbl(m[7], m[3]);
+  fp pre[KZGP_DIGITS];
+  pre[0] = m[0].z;
+  for (int d = 1; d < KZGP_DIGITS; d++) fp_mul(pre[d], pre[d - 1], m[d].z);
+  fp inv;
+  fp_inv(inv, pre[KZGP_DIGITS - 1]);
+  for (int d = KZGP_DIGITS - 1; d >= 0; d--) {
+    fp zi, zi2, zi3;
+    if (d > 0)
+      fp_mul(zi, inv, pre[d - 1]);
+    else
+      zi = inv;
+    fp_mul(inv, inv, m[d].z);
+    fp_sqr(zi2, zi);
+    fp_mul(zi3, zi2, zi);
+    g1t out;
+    fp_mul(out.x, m[d].x, zi2);
+    fp_mul(out.y, m[d].y, zi3);
+    table[(uint64_t)lane * KZGP_DIGITS + d] = out;
+  }
+}
+
+// compute_kzg_proof_impl's quotient in evaluation form, k_kzg_eval's shape
+// (one block per blob, 16 elements per thread, one inversion per thread).
+// z = w_m: q_m = sum_{i != m} (f_i - y) w_i / (z (z - w_i))
+//              = -(1/z) sum_{i != m} q_i w_i.
+// Scalars leave as canonical big-endian bytes, the blob's own format.
+__global__ __launch_bounds__(256) void k_kzgp_quotient(
+    const uint8_t *__restrict__ blobs, uint64_t n, KzgWork w,
+    uint8_t *__restrict__ qs) {
+  __shared__ fr lds[256];
+  __shared__ int s_m;
+  uint64_t b = blockIdx.x;
+  int t = threadIdx.x;
+  if (b >= n) return;
+  const uint8_t *blob = blobs + b * KZG_BLOB_BYTES;
+  uint8_t *q_out = qs + b * KZG_BLOB_BYTES;
+  if (t == 0) s_m = -1;
+  __syncthreads();
+  fr z, y;
+  // a non-canonical z or y was flagged by k_kzg_eval; the call has failed
+  if (!fr_from_be32(z, w.zs + 32 * b)) fr_zero(z);
+  if (!fr_from_be32(y, w.ys + 32 * b)) fr_zero(y);
+  fr omega, w16, base;
+#pragma unroll
+  for (int i = 0; i < 8; i++) omega.v[i] = FR_OMEGA_MONT[i];
+  w16 = omega;
+  for (int i = 0; i < 8; i++) fr_sqr(w16, w16); // omega^256
+  uint32_t e = bitrev_lo((uint32_t)t, 8);
+  fr_pow(base, omega, &e, 1);
+  fr num[16], den[16], pre[16];
+  fr g, run;
+  fr_one(g);
+  fr_one(run);
+  int hit = -1;
+  for (int mi = 0; mi < 16; mi++) {
+    int k = (int)bitrev_lo((uint32_t)mi, 4);
+    uint32_t j = 16u * (uint32_t)t + (uint32_t)k;
+    fr f, wk, d;
+    if (!fr_from_be32(f, blob + 32 * j)) fr_zero(f); // flagged by k_kzg_eval
+    fr_mul(wk, base, g); // omega^bitrev12(j)
+    fr_mul(g, g, w16);
+    fr_sub(d, wk, z);
+    fr_sub(num[mi], f, y);
+    if (fr_is_zero(d)) { // z = w_j: this element takes the in-domain term
+      s_m = (int)j;
+      hit = mi;
+      fr_one(d);
+    }
+    den[mi] = d;
+    fr_mul(run, run, d);
+    pre[mi] = run;
+  }
+  fr inv, acc;
+  fr_inv(inv, run);
+  fr_zero(acc);
+  for (int mi = 15; mi >= 0; mi--) {
+    int k = (int)bitrev_lo((uint32_t)mi, 4);
+    uint32_t j = 16u * (uint32_t)t + (uint32_t)k;
+    fr id, q, wk, term;
+    if (mi > 0)
+      fr_mul(id, inv, pre[mi - 1]);
+    else
+      id = inv;
+    fr_mul(inv, inv, den[mi]);
+    if (mi == hit) continue;
+    fr_mul(q, num[mi], id);
+    fr_to_be32(q, q_out + 32 * j);
+    fr_add(wk, den[mi], z);
+    fr_mul(term, q, wk);
+    fr_add(acc, acc, term);
+  }
+  lds[t] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s) {
+      fr a;
+      fr_add(a, lds[t], lds[t + s]);
+      lds[t] = a;
+    }
+    __syncthreads();
+  }
+  if (t == 0 && s_m >= 0) {
+    fr zi, q;
+    fr_inv(zi, z); // z is a root of unity here, never zero
+    fr_mul(q, lds[0], zi);
+    fr_neg(q, q);
+    fr_to_be32(q, q_out + 32 * (uint32_t)s_m);
+  }
+}
+
+// the MSM's look-up stage. Lane (element e, quarter q) owns windows
+// 16q..16q+15 of scalar e. Signed recoding d = nibble + carry, d > 8 =>
+// d - 16 and carry 1; the carry into window k is 1 exactly when the low k
+// nibbles exceed 0x88..8 (the largest value k digits <= 8 can hold), so
+// each quarter finds its carry-in without walking the windows below it.
+// A scalar is < r < 2^255: the top nibble is <= 7 and never carries out.
+// The 256 lane sums of a block are joined in LDS; every addition takes the
+// doubling, inverse and infinity branches of g1j_add / g1j_add_aff.
+__global__ __launch_bounds__(256) void k_kzgp_msm(
+    const uint8_t *__restrict__ scalars, const g1t *__restrict__ table,
+    g1j *__restrict__ partial, int *__restrict__ fail) {
+  __shared__ g1j lds[256];
+  uint32_t t = threadIdx.x;
+  uint32_t lane = blockIdx.x * 256 + t; // < 16384
+  uint32_t e = lane >> 2, q = lane & 3;
+  uint64_t blob = blockIdx.y;
+  uint32_t s[8];
+  fr_limbs_from_be32(s, scalars + (blob * KZG_N + e) * 32);
+  if (fr_ge_r(s)) { // non-canonical blob element
+    if (q == 0) atomicOr(fail, 1);
+#pragma unroll
+    for (int i = 0; i < 8; i++) s[i] = 0;
+  }
+  bool gt = false;
+  uint32_t carry_in[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    gt = s[i] > 0x88888888u || (s[i] == 0x88888888u && gt);
+    if (i & 1) carry_in[(i + 1) >> 1] = gt ? 1u : 0u;
+  }
+  uint32_t lo = s[0], hi = s[1], carry = 0;
+#pragma unroll
+  for (int k = 1; k < 4; k++)
+    if (q == (uint32_t)k) {
+      lo = s[2 * k];
+      hi = s[2 * k + 1];
+      carry = carry_in[k];
+    }
+  uint64_t bits = ((uint64_t)hi << 32) | lo;
+  g1j acc;
+  g1j_set_inf(acc);
+  for (uint32_t k = 0; k < KZGP_PER_LANE; k++) {
+    int d = (int)((bits >> (4 * k)) & 15) + (int)carry;
+    carry = d > 8 ? 1u : 0u;
+    if (carry) d -= 16;
+    if (d == 0) continue;
+    uint32_t mag = (uint32_t)(d < 0 ? -d : d); // 1..8
+    uint32_t j = KZGP_PER_LANE * q + k;
+    const g1t &tp =
+        table[((uint64_t)j * KZG_N + e) * KZGP_DIGITS + (mag - 1)];
+    g1a pt;
+    pt.x = tp.x;
+    pt.y = tp.y;
+    pt.inf = 0;
+    if (d < 0) fp_neg(pt.y, pt.y);
+    g1j_add_aff(acc, acc, pt);
+  }
+  lds[t] = acc;
+  __syncthreads();
+  for (uint32_t st = 128; st > 0; st >>= 1) {
+    if (t < st) {
+      g1j sum;
+      g1j_add(sum, lds[t], lds[t + st]);
+      lds[t] = sum;
+    }
+    __syncthreads();
+  }
+  if (t == 0) partial[blob * KZGP_BLOCKS + blockIdx.x] = lds[0];
+}
+
+// one block per blob: the KZGP_BLOCKS partial sums, then the wire form
+__global__ __launch_bounds__(KZGP_BLOCKS) void k_kzgp_finish(
+    const g1j *__restrict__ partial, uint8_t *__restrict__ out) {
+  __shared__ g1j lds[KZGP_BLOCKS];
+  uint32_t t = threadIdx.x;
+  uint64_t blob = blockIdx.x;
+  lds[t] = partial[blob * KZGP_BLOCKS + t];
+  __syncthreads();
+  for (uint32_t st = KZGP_BLOCKS / 2; st > 0; st >>= 1) {
+    if (t < st) {
+      g1j sum;
+      g1j_add(sum, lds[t], lds[t + st]);
+      lds[t] = sum;
+    }
+    __syncthreads();
+  }
+  if (t == 0) g1_compress(out + 48 * blob, lds[0]);
+}
+
+// commitment validation for compute_blob_kzg_proof: one lane per point
+__global__ __launch_bounds__(64, 1) void k_kzgp_check_g1(
+    const uint8_t *__restrict__ cs, uint64_t n, int *__restrict__ fail) {
+  uint64_t lane = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (lane >= n) return;
+  g1a p;
+  if (!kzg_validate_g1(p, cs + 48 * lane)) atomicOr(fail, 1);
+}
+
+struct KzgpWork {
+  uint8_t *qs;   // [n*131072] quotient scalars, canonical BE
+  g1j *partial;  // [n*KZGP_BLOCKS] block sums of the MSM
+};
+
+int kzgp_layout(m3x_ctx *ctx, uint64_t n, bool quotient, KzgpWork &p) {
+  uint64_t part = (n * KZGP_BLOCKS * sizeof(g1j) + 255) & ~255ull;
+  uint64_t bytes = part + (quotient ? n * KZG_BLOB_BYTES : 0);
+  int rc = m3x::ensure_scratch(ctx, &ctx->scratch_b, &ctx->scratch_b_bytes,
+                               bytes);
+  if (rc != M3X_OK) return rc;
+  p.partial = reinterpret_cast<g1j *>(ctx->scratch_b);
+  p.qs = ctx->scratch_b + part;
+  return M3X_OK;
+}
+
+bool kzgp_args_ok(m3x_ctx *ctx, m3x_kzg *kzg, uint64_t n) {
+  return kzg_args_ok(ctx, kzg, n) && kzg->table;
+}
+
+// n MSMs over the handle's table: scalars_dev n*4096*32 BE, out_dev n*48
+void launch_msm(m3x_ctx *ctx, m3x_kzg *kzg, const KzgWork &w,
+                const KzgpWork &p, const uint8_t *scalars_dev, uint64_t n,
+                uint8_t *out_dev) {
+  m3x::time_begin(ctx, M3X_K_KZGP_MSM);
+  hipLaunchKernelGGL(k_kzgp_msm, dim3(KZGP_BLOCKS, (uint32_t)n), dim3(256), 0,
+                     ctx->stream, scalars_dev, kzg->table, p.partial, w.fail);
+  m3x::time_end(ctx, M3X_K_KZGP_MSM);
+  m3x::time_begin(ctx, M3X_K_KZGP_FINISH);
+  hipLaunchKernelGGL(k_kzgp_finish, dim3((uint32_t)n), dim3(KZGP_BLOCKS), 0,
+                     ctx->stream, p.partial, out_dev);
+  m3x::time_end(ctx, M3X_K_KZGP_FINISH);
+}
+
+// quotient + MSM once w.zs and w.ys hold z and y
+void launch_quotient_msm(m3x_ctx *ctx, m3x_kzg *kzg, const KzgWork &w,
+                         const KzgpWork &p, const uint8_t *blobs_dev,
+                         uint64_t n, uint8_t *out_dev) {
+  m3x::time_begin(ctx, M3X_K_KZGP_QUOTIENT);
+  hipLaunchKernelGGL(k_kzgp_quotient, dim3((uint32_t)n), dim3(256), 0,
+                     ctx->stream, blobs_dev, n, w, p.qs);
+  m3x::time_end(ctx, M3X_K_KZGP_QUOTIENT);
+  launch_msm(ctx, kzg, w, p, p.qs, n, out_dev);
+}
+
+// read the failure flag back after everything queued on the main stream
+int kzgp_wait(m3x_ctx *ctx, const KzgWork &w) {
+  int32_t fail = 1;
+  M3X_HIP_CHECK(
+      hipMemcpyAsync(&fail, w.fail, 4, hipMemcpyDeviceToHost, ctx->stream));
+  M3X_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return fail ? M3X_ERR_ENCODING : M3X_OK;
+}
+
+// run a *_dev entry over host buffers: ins[i] (in_bytes[i]) are uploaded,
+// outs[i] (out_bytes[i]) downloaded after a successful call
+template <typename F>
+int32_t kzgp_host_call(const uint8_t *const *ins, const uint64_t *in_bytes,
+                       int n_in, uint8_t *const *outs,
+                       const uint64_t *out_bytes, int n_out, F call) {
+  uint8_t *d[6] = {};
+  int32_t rc = M3X_ERR_HIP;
+  bool ok = true;
+  for (int i = 0; i < n_in && ok; i++)
+    ok = (d[i] = dev_copy(ins[i], in_bytes[i])) != nullptr;
+  for (int i = 0; i < n_out && ok; i++)
+    ok = hipMalloc(&d[n_in + i], out_bytes[i]) == hipSuccess;
+  if (ok) rc = call(d);
+  for (int i = 0; i < n_out && rc == M3X_OK; i++)
+    if (hipMemcpy(outs[i], d[n_in + i], out_bytes[i],
+                  hipMemcpyDeviceToHost) != hipSuccess)
+      rc = M3X_ERR_HIP;
+  for (int i = 0; i < n_in + n_out; i++)
+    if (d[i]) (void)hipFree(d[i]);
+  return rc;
+}
+
 } // namespace
 
 extern "C" {
@@ -620,9 +992,202 @@ out:
 
 void m3x_kzg_destroy(m3x_kzg *kzg) {
   if (!kzg) return;
-  if (kzg->g2 && hipSetDevice(kzg->device) == hipSuccess)
-    (void)hipFree(kzg->g2);
+  if (hipSetDevice(kzg->device) == hipSuccess) {
+    if (kzg->g2) (void)hipFree(kzg->g2);
+    if (kzg->table) (void)hipFree(kzg->table);
+  }
   delete kzg;
+}
+
+int32_t m3x_kzgp_load_g1_lagrange(m3x_ctx *ctx, m3x_kzg *kzg,
+                                  const uint8_t *g1_lagrange) {
+  if (!kzg_args_ok(ctx, kzg, 0) || !g1_lagrange || kzg->table)
+    return M3X_ERR_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  M3X_HIP_CHECK(hipSetDevice(ctx->device));
+  uint8_t *lag_d = dev_copy(g1_lagrange, (uint64_t)KZG_N * 48);
+  g1j *bases = nullptr;
+  g1t *table = nullptr;
+  int *fail_d = nullptr;
+  int fail = 1;
+  int32_t rc = M3X_ERR_HIP;
+  if (!lag_d) goto out;
+  if (hipMalloc(&fail_d, 4) != hipSuccess) goto out;
+  rc = M3X_ERR_NOMEM;
+  if (hipMalloc(&bases, (uint64_t)KZGP_WINDOWS * KZG_N * sizeof(g1j)) !=
+      hipSuccess)
+    goto out;
+  if (hipMalloc(&table, KZGP_TABLE_POINTS * sizeof(g1t)) != hipSuccess)
+    goto out;
+  rc = M3X_ERR_HIP;
+  if (hipMemsetAsync(fail_d, 0, 4, ctx->stream) != hipSuccess) goto out;
+  hipLaunchKernelGGL(k_kzgp_bases, dim3(KZG_N / 64), dim3(64), 0, ctx->stream,
+                     lag_d, bases, fail_d);
+  if (hipMemcpyAsync(&fail, fail_d, 4, hipMemcpyDeviceToHost, ctx->stream) !=
+      hipSuccess)
+    goto out;
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) goto out;
+  if (fail) {
+    rc = M3X_ERR_ENCODING;
+    goto out;
+  }
+  hipLaunchKernelGGL(k_kzgp_table, dim3(KZGP_WINDOWS * KZG_N / 64), dim3(64),
+                     0, ctx->stream, bases, table);
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) goto out;
+  rc = M3X_OK;
+out:
+  if (lag_d) (void)hipFree(lag_d);
+  if (fail_d) (void)hipFree(fail_d);
+  if (bases) (void)hipFree(bases);
+  if (rc != M3X_OK) {
+    if (table) (void)hipFree(table);
+    return rc;
+  }
+  kzg->table = table;
+  return M3X_OK;
+}
+
+int32_t m3x_kzgp_blob_to_commitment_dev(m3x_ctx *ctx, m3x_kzg *kzg,
+                                        const void *blobs_dev, uint64_t n,
+                                        void *out_dev) {
+  if (!kzgp_args_ok(ctx, kzg, n)) return M3X_ERR_ARG;
+  if (n == 0) return M3X_OK;
+  if (!blobs_dev || !out_dev) return M3X_ERR_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  M3X_HIP_CHECK(hipSetDevice(ctx->device));
+  KzgWork w;
+  KzgpWork p;
+  int rc = kzg_layout(ctx, n, w);
+  if (rc == M3X_OK) rc = kzgp_layout(ctx, n, false, p);
+  if (rc != M3X_OK) return rc;
+  M3X_HIP_CHECK(hipMemsetAsync(w.fail, 0, 4, ctx->stream));
+  // the MSM digits come straight from the blob bytes
+  launch_msm(ctx, kzg, w, p, (const uint8_t *)blobs_dev, n,
+             (uint8_t *)out_dev);
+  return kzgp_wait(ctx, w);
+}
+
+int32_t m3x_kzgp_blob_to_commitment(m3x_ctx *ctx, m3x_kzg *kzg,
+                                    const uint8_t *blobs, uint64_t n,
+                                    uint8_t *out) {
+  if (!kzgp_args_ok(ctx, kzg, n)) return M3X_ERR_ARG;
+  if (n == 0) return M3X_OK;
+  if (!blobs || !out) return M3X_ERR_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  M3X_HIP_CHECK(hipSetDevice(ctx->device));
+  const uint8_t *ins[1] = {blobs};
+  uint64_t in_bytes[1] = {n * KZG_BLOB_BYTES};
+  uint8_t *outs[1] = {out};
+  uint64_t out_bytes[1] = {n * 48};
+  return kzgp_host_call(ins, in_bytes, 1, outs, out_bytes, 1,
+                        [&](uint8_t **d) {
+                          return m3x_kzgp_blob_to_commitment_dev(ctx, kzg, d[0],
+                                                                 n, d[1]);
+                        });
+}
+
+int32_t m3x_kzgp_compute_proof_dev(m3x_ctx *ctx, m3x_kzg *kzg,
+                                   const void *blobs_dev, const void *zs_dev,
+                                   uint64_t n, void *proofs_out_dev,
+                                   void *ys_out_dev) {
+  if (!kzgp_args_ok(ctx, kzg, n)) return M3X_ERR_ARG;
+  if (n == 0) return M3X_OK;
+  if (!blobs_dev || !zs_dev || !proofs_out_dev || !ys_out_dev)
+    return M3X_ERR_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  M3X_HIP_CHECK(hipSetDevice(ctx->device));
+  KzgWork w;
+  KzgpWork p;
+  int rc = kzg_layout(ctx, n, w);
+  if (rc == M3X_OK) rc = kzgp_layout(ctx, n, true, p);
+  if (rc != M3X_OK) return rc;
+  M3X_HIP_CHECK(hipMemsetAsync(w.fail, 0, 4, ctx->stream));
+  rc = launch_challenge_eval(ctx, w, (const uint8_t *)blobs_dev, nullptr,
+                             (const uint8_t *)zs_dev, n);
+  if (rc != M3X_OK) return rc;
+  launch_quotient_msm(ctx, kzg, w, p, (const uint8_t *)blobs_dev, n,
+                      (uint8_t *)proofs_out_dev);
+  M3X_HIP_CHECK(hipMemcpyAsync(ys_out_dev, w.ys, n * 32,
+                               hipMemcpyDeviceToDevice, ctx->stream));
+  return kzgp_wait(ctx, w);
+}
+
+int32_t m3x_kzgp_compute_proof(m3x_ctx *ctx, m3x_kzg *kzg,
+                               const uint8_t *blobs, const uint8_t *zs,
+                               uint64_t n, uint8_t *proofs_out,
+                               uint8_t *ys_out) {
+  if (!kzgp_args_ok(ctx, kzg, n)) return M3X_ERR_ARG;
+  if (n == 0) return M3X_OK;
+  if (!blobs || !zs || !proofs_out || !ys_out) return M3X_ERR_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  M3X_HIP_CHECK(hipSetDevice(ctx->device));
+  const uint8_t *ins[2] = {blobs, zs};
+  uint64_t in_bytes[2] = {n * KZG_BLOB_BYTES, n * 32};
+  uint8_t *outs[2] = {proofs_out, ys_out};
+  uint64_t out_bytes[2] = {n * 48, n * 32};
+  return kzgp_host_call(ins, in_bytes, 2, outs, out_bytes, 2,
+                        [&](uint8_t **d) {
+                          return m3x_kzgp_compute_proof_dev(ctx, kzg, d[0],
+                                                            d[1], n, d[2],
+                                                            d[3]);
+                        });
+}
+
+int32_t m3x_kzgp_compute_blob_proof_dev(m3x_ctx *ctx, m3x_kzg *kzg,
+                                        const void *blobs_dev,
+                                        const void *cs_dev, uint64_t n,
+                                        void *out_dev) {
+  if (!kzgp_args_ok(ctx, kzg, n)) return M3X_ERR_ARG;
+  if (n == 0) return M3X_OK;
+  if (!blobs_dev || !cs_dev || !out_dev) return M3X_ERR_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  M3X_HIP_CHECK(hipSetDevice(ctx->device));
+  KzgWork w;
+  KzgpWork p;
+  int rc = kzg_layout(ctx, n, w);
+  if (rc == M3X_OK) rc = kzgp_layout(ctx, n, true, p);
+  if (rc != M3X_OK) return rc;
+  M3X_HIP_CHECK(hipMemsetAsync(w.fail, 0, 4, ctx->stream));
+  // the commitment check feeds nothing but the failure flag: it runs on
+  // stream3 beside the whole challenge -> eval -> quotient -> MSM chain
+  M3X_HIP_CHECK(hipEventRecord(ctx->ev_pipe[0], ctx->stream));
+  M3X_HIP_CHECK(hipStreamWaitEvent(ctx->stream3, ctx->ev_pipe[0], 0));
+  m3x::time_begin_s(ctx, M3X_K_KZG_DECOMP, ctx->stream3);
+  hipLaunchKernelGGL(k_kzgp_check_g1, dim3((uint32_t)((n + 63) / 64)),
+                     dim3(64), 0, ctx->stream3, (const uint8_t *)cs_dev, n,
+                     w.fail);
+  m3x::time_end_s(ctx, M3X_K_KZG_DECOMP, ctx->stream3);
+  M3X_HIP_CHECK(hipEventRecord(ctx->ev_pipe[1], ctx->stream3));
+  rc = launch_challenge_eval(ctx, w, (const uint8_t *)blobs_dev,
+                             (const uint8_t *)cs_dev, nullptr, n);
+  if (rc == M3X_OK)
+    launch_quotient_msm(ctx, kzg, w, p, (const uint8_t *)blobs_dev, n,
+                        (uint8_t *)out_dev);
+  if (hipStreamWaitEvent(ctx->stream, ctx->ev_pipe[1], 0) != hipSuccess)
+    rc = M3X_ERR_HIP;
+  int rc2 = kzgp_wait(ctx, w);
+  (void)hipStreamSynchronize(ctx->stream2);
+  (void)hipStreamSynchronize(ctx->stream3);
+  return rc != M3X_OK ? rc : rc2;
+}
+
+int32_t m3x_kzgp_compute_blob_proof(m3x_ctx *ctx, m3x_kzg *kzg,
+                                    const uint8_t *blobs, const uint8_t *cs,
+                                    uint64_t n, uint8_t *out) {
+  if (!kzgp_args_ok(ctx, kzg, n)) return M3X_ERR_ARG;
+  if (n == 0) return M3X_OK;
+  if (!blobs || !cs || !out) return M3X_ERR_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  M3X_HIP_CHECK(hipSetDevice(ctx->device));
+  const uint8_t *ins[2] = {blobs, cs};
+  uint64_t in_bytes[2] = {n * KZG_BLOB_BYTES, n * 48};
+  uint8_t *outs[1] = {out};
+  uint64_t out_bytes[1] = {n * 48};
+  return kzgp_host_call(ins, in_bytes, 2, outs, out_bytes, 1,
+                        [&](uint8_t **d) {
+                          return m3x_kzgp_compute_blob_proof_dev(
+                              ctx, kzg, d[0], d[1], n, d[2]);
+                        });
 }
 
 int32_t m3x_kzg_verify_proof_batch(m3x_ctx *ctx, m3x_kzg *kzg,

@@ -1,14 +1,18 @@
-"""KZG blob proof verification on the GPU — the verification half of the
-reference's `Kzg` wrapper (crypto/kzg/src/lib.rs:62-167): verify_kzg_proof,
-verify_blob_kzg_proof and verify_blob_kzg_proof_batch.
+"""KZG on the GPU — the reference's `Kzg` wrapper
+(crypto/kzg/src/lib.rs:62-167): verify_kzg_proof, verify_blob_kzg_proof and
+verify_blob_kzg_proof_batch, and the producing half blob_to_kzg_commitment,
+compute_kzg_proof and compute_blob_kzg_proof.
 
 Verification needs one trusted-setup point, [tau]G2 (entry 1 of the
-ceremony's g2_monomial list, 96 bytes compressed). All byte strings are the
-spec's big-endian wire forms. Every method returns a bool: a proof that
-does not verify is False; malformed input (bad point encoding, a point
-outside the subgroup, a scalar >= the field modulus, wrong lengths)
-raises KzgError, the analogue of the reference's Error::Kzg /
-InconsistentArrayLength. No CPU fallback (package rule)."""
+ceremony's g2_monomial list, 96 bytes compressed). Producing commitments
+and proofs also needs the 4096 g1_lagrange points, in the ceremony file's
+order; without them the handle is verification-only. All byte strings are
+the spec's big-endian wire forms. Every verify method returns a bool: a
+proof that does not verify is False; malformed input (bad point encoding, a
+point outside the subgroup, a scalar >= the field modulus, wrong lengths)
+or a producing call without the Lagrange basis raises KzgError, the
+analogue of the reference's Error::Kzg / InconsistentArrayLength. No CPU
+fallback (package rule)."""
 import ctypes
 from typing import Optional, Sequence
 
@@ -46,11 +50,36 @@ def _verdict(rc, what):
     raise RuntimeError(f"{what} failed (rc={rc})")
 
 
-class Kzg:
-    """Verification-side trusted setup, bound to one GPU context."""
+def _join(name, items, want):
+    return b"".join(_check_len(name, b, want) for b in items)
 
-    def __init__(self, g2_tau: bytes, ctx: Optional[_native.Ctx] = None):
+
+def _split(raw, size, n):
+    return [raw[size * i : size * (i + 1)] for i in range(n)]
+
+
+class Kzg:
+    """Trusted setup bound to one GPU context: [tau]G2 for verification,
+    plus (optionally) the Lagrange basis for commitments and proofs. The
+    basis costs a one-time table build and about 200 MB of device memory."""
+
+    def __init__(self, g2_tau: bytes, g1_lagrange=None,
+                 ctx: Optional[_native.Ctx] = None):
         g2_tau = _check_len("g2_tau", g2_tau, BYTES_PER_G2_POINT)
+        if g1_lagrange is not None:
+            if not isinstance(g1_lagrange, (bytes, bytearray)):
+                if len(g1_lagrange) != FIELD_ELEMENTS_PER_BLOB:
+                    raise KzgError(
+                        f"g1_lagrange: expected {FIELD_ELEMENTS_PER_BLOB} "
+                        f"points, got {len(g1_lagrange)}"
+                    )
+                g1_lagrange = _join("g1_lagrange point", g1_lagrange,
+                                    BYTES_PER_COMMITMENT)
+            g1_lagrange = _check_len(
+                "g1_lagrange", g1_lagrange,
+                FIELD_ELEMENTS_PER_BLOB * BYTES_PER_COMMITMENT,
+            )
+        self._has_basis = False
         self._ctx = ctx or _native.default_ctx()
         self._lib = _native.load()
         self._h = ctypes.c_void_p()
@@ -61,6 +90,20 @@ class Kzg:
             raise KzgError("g2_tau is not a valid non-infinity G2 subgroup point")
         if rc != 0:
             raise RuntimeError(f"m3x_kzg_create failed (rc={rc})")
+        if g1_lagrange is not None:
+            rc = self._lib.m3x_kzgp_load_g1_lagrange(
+                self._ctx.handle, self._h, g1_lagrange
+            )
+            if rc != 0:
+                self.close()
+            if rc == _ERR_ENCODING:
+                raise KzgError(
+                    "g1_lagrange holds a point that is not a valid "
+                    "non-infinity G1 subgroup point"
+                )
+            if rc != 0:
+                raise RuntimeError(f"m3x_kzgp_load_g1_lagrange failed (rc={rc})")
+            self._has_basis = True
 
     def close(self):
         if getattr(self, "_h", None):
@@ -138,6 +181,110 @@ class Kzg:
             self._ctx.handle, self._h, blobs_dev, commitments_dev, proofs_dev, n
         )
         return _verdict(rc, "verify_blob_kzg_proof_batch_dev")
+
+
+    # ---- producing half ----
+    def _produced(self, rc, what):
+        if rc == _ERR_ENCODING:
+            raise KzgError(f"{what}: malformed point or non-canonical field element")
+        if rc != 0:
+            raise RuntimeError(f"{what} failed (rc={rc})")
+
+    def _need_basis(self, what):
+        if not self._has_basis:
+            raise KzgError(f"{what}: this Kzg was built without g1_lagrange")
+
+    # ---- lib.rs:134-139 ----
+    def blob_to_kzg_commitment(self, blob: bytes) -> bytes:
+        return self.blob_to_kzg_commitment_batch([blob])[0]
+
+    def blob_to_kzg_commitment_batch(self, blobs: Sequence[bytes]):
+        self._need_basis("blob_to_kzg_commitment")
+        n = len(blobs)
+        if n == 0:
+            return []
+        bl = _join("blob", blobs, BYTES_PER_BLOB)
+        out = ctypes.create_string_buffer(BYTES_PER_COMMITMENT * n)
+        rc = self._lib.m3x_kzgp_blob_to_commitment(
+            self._ctx.handle, self._h, bl, n, out
+        )
+        self._produced(rc, "blob_to_kzg_commitment")
+        return _split(out.raw, BYTES_PER_COMMITMENT, n)
+
+    # ---- lib.rs:141-150 ----
+    def compute_kzg_proof(self, blob: bytes, z: bytes):
+        """(proof, y) with y = p(z)."""
+        return self.compute_kzg_proof_batch([blob], [z])[0]
+
+    def compute_kzg_proof_batch(self, blobs: Sequence[bytes],
+                                zs: Sequence[bytes]):
+        self._need_basis("compute_kzg_proof")
+        n = len(blobs)
+        if n != len(zs):
+            raise KzgError(f"inconsistent array length: {n} blobs, {len(zs)} zs")
+        if n == 0:
+            return []
+        bl = _join("blob", blobs, BYTES_PER_BLOB)
+        zb = _join("z", zs, BYTES_PER_FIELD_ELEMENT)
+        proofs = ctypes.create_string_buffer(BYTES_PER_PROOF * n)
+        ys = ctypes.create_string_buffer(BYTES_PER_FIELD_ELEMENT * n)
+        rc = self._lib.m3x_kzgp_compute_proof(
+            self._ctx.handle, self._h, bl, zb, n, proofs, ys
+        )
+        self._produced(rc, "compute_kzg_proof")
+        return list(zip(_split(proofs.raw, BYTES_PER_PROOF, n),
+                        _split(ys.raw, BYTES_PER_FIELD_ELEMENT, n)))
+
+    # ---- lib.rs:72-81 ----
+    def compute_blob_kzg_proof(self, blob: bytes, commitment: bytes) -> bytes:
+        return self.compute_blob_kzg_proof_batch([blob], [commitment])[0]
+
+    def compute_blob_kzg_proof_batch(self, blobs: Sequence[bytes],
+                                     commitments: Sequence[bytes]):
+        self._need_basis("compute_blob_kzg_proof")
+        n = len(blobs)
+        if n != len(commitments):
+            raise KzgError(
+                f"inconsistent array length: {n} blobs, {len(commitments)} commitments"
+            )
+        if n == 0:
+            return []
+        bl = _join("blob", blobs, BYTES_PER_BLOB)
+        cs = _join("commitment", commitments, BYTES_PER_COMMITMENT)
+        out = ctypes.create_string_buffer(BYTES_PER_PROOF * n)
+        rc = self._lib.m3x_kzgp_compute_blob_proof(
+            self._ctx.handle, self._h, bl, cs, n, out
+        )
+        self._produced(rc, "compute_blob_kzg_proof")
+        return _split(out.raw, BYTES_PER_PROOF, n)
+
+    def blob_to_kzg_commitment_batch_dev(self, blobs_dev, n: int, out_dev):
+        """Device-resident form: blobs n*131072 -> out_dev n*48."""
+        self._need_basis("blob_to_kzg_commitment")
+        rc = self._lib.m3x_kzgp_blob_to_commitment_dev(
+            self._ctx.handle, self._h, blobs_dev, n, out_dev
+        )
+        self._produced(rc, "blob_to_kzg_commitment_dev")
+
+    def compute_kzg_proof_batch_dev(self, blobs_dev, zs_dev, n: int,
+                                    proofs_out_dev, ys_out_dev):
+        """Device-resident form: blobs n*131072, zs n*32 -> proofs n*48
+        and ys n*32."""
+        self._need_basis("compute_kzg_proof")
+        rc = self._lib.m3x_kzgp_compute_proof_dev(
+            self._ctx.handle, self._h, blobs_dev, zs_dev, n, proofs_out_dev,
+            ys_out_dev
+        )
+        self._produced(rc, "compute_kzg_proof_dev")
+
+    def compute_blob_kzg_proof_batch_dev(self, blobs_dev, commitments_dev,
+                                         n: int, out_dev):
+        """Device-resident form: blobs n*131072, commitments n*48 -> n*48."""
+        self._need_basis("compute_blob_kzg_proof")
+        rc = self._lib.m3x_kzgp_compute_blob_proof_dev(
+            self._ctx.handle, self._h, blobs_dev, commitments_dev, n, out_dev
+        )
+        self._produced(rc, "compute_blob_kzg_proof_dev")
 
 
 # ---- test/introspection seams (parity tests; not on the import path) ----

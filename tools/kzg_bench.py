@@ -12,7 +12,16 @@ Inputs are three distinct seed-derived blobs cycled to n, with commitments
 and proofs made under the insecure test setup of
 tests/golden/kzg_fixtures.json (CPU oracle: test infrastructure). Needs a
 GPU; there is no fallback. No CPU KZG implementation exists in this tree,
-so no CPU ratio is computed."""
+so no CPU ratio is computed.
+
+--prove times the producing half instead, by the same method, for n = 1 and
+6: blob_to_kzg_commitment and compute_blob_kzg_proof over device-resident
+inputs and outputs, under the known-tau test setup ([L_i(tau)]G1 from the
+CPU oracle). It first reports the one-time Lagrange load (validation +
+table build), and beside each producing result it prints the kzg_mults
+kernel time of a verification run of the same n in the same process: the
+per-lane 255-step chain the MSM kernels (kzgp_msm + kzgp_finish) are
+measured against."""
 import argparse
 import ctypes
 import hashlib
@@ -61,18 +70,123 @@ def make_triples(g2_seed):
     return out
 
 
+def make_lagrange(g2_seed):
+    """[L_k(tau)]G1 compressed, in trusted-setup file order."""
+    import gen_bls_fixtures as G
+    import kzg_prover_ref as P
+    import kzg_ref as K
+
+    oracle = ctypes.CDLL(str(REPO / "oracle" / "liboracle.so"))
+    tau = int.from_bytes(hashlib.sha256(g2_seed.encode()).digest(), "big") % K.R
+    gen = G.g1_uncompressed(G.G1G)
+    out = []
+    for s in P.lagrange_scalars_file_order(tau):
+        buf = ctypes.create_string_buffer(96)
+        assert oracle.m3x_oracle_bls_g1_mul(gen, s.to_bytes(32, "big"), buf) == 0
+        raw = buf.raw
+        out.append(G.g1_compress(
+            (int.from_bytes(raw[:48], "big"), int.from_bytes(raw[48:], "big"))))
+    return b"".join(out)
+
+
+def timed(ctx, run, reps, warmup):
+    """(host-clock times of `reps` calls, per-kernel ms from a separate
+    pass with event timing on) - the verify mode's method."""
+    for _ in range(warmup):
+        run()
+    times = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        run()
+        times.append(time.perf_counter() - t0)
+    ctx.timing_enable(True)
+    kreps = max(3, reps // 4)
+    for _ in range(kreps):
+        run()
+    kernels = {
+        name: round(ms / kreps, 4)
+        for name, (ms, launches) in ctx.kernel_times().items()
+        if name.startswith("kzg") and launches
+    }
+    ctx.timing_enable(False)
+    return times, kernels
+
+
+def prove_main(args, fx, triples, ctx, kzg):
+    g2_tau = bytes.fromhex(fx["test_setup"]["g2_tau"])
+    lagrange = make_lagrange(fx["test_setup"]["tau_seed"])
+    t0 = time.perf_counter()
+    k = kzg.Kzg(g2_tau, lagrange, ctx=ctx)
+    load_ms = (time.perf_counter() - t0) * 1e3
+    table_bytes = 64 * 4096 * 8 * 96
+    print(json.dumps({
+        "setup_load_ms": round(load_ms, 2),
+        "table_bytes": table_bytes,
+        "table_MB": round(table_bytes / 1e6, 1),
+    }), flush=True)
+    for n in [int(s) for s in args.sizes.split(",")]:
+        ts = [triples[i % 3] for i in range(n)]
+        blobs_d = ctx.upload(b"".join(t[0] for t in ts))
+        cs_d = ctx.upload(b"".join(t[1] for t in ts))
+        ps_d = ctx.upload(b"".join(t[2] for t in ts))
+        out_d = ctx.alloc(48 * n)
+        want_c = b"".join(t[1] for t in ts)
+        want_p = b"".join(t[2] for t in ts)
+
+        def check(want):
+            got = ctypes.create_string_buffer(48 * n)
+            assert ctx._lib.m3x_d2h(ctx.handle, got, out_d, 48 * n) == 0
+            assert got.raw == want, "producer output differs from the oracle's"
+
+        def verify():
+            assert k.verify_blob_kzg_proof_batch_dev(blobs_d, cs_d, ps_d, n) is True
+
+        _, vk = timed(ctx, verify, max(4, args.reps // 4), 1)
+        for what, run, want in (
+            ("blob_to_kzg_commitment",
+             lambda: k.blob_to_kzg_commitment_batch_dev(blobs_d, n, out_d), want_c),
+            ("compute_blob_kzg_proof",
+             lambda: k.compute_blob_kzg_proof_batch_dev(blobs_d, cs_d, n, out_d), want_p),
+        ):
+            times, kernels = timed(ctx, run, args.reps, args.warmup)
+            check(want)
+            med = statistics.median(times)
+            msm = kernels.get("kzgp_msm", 0.0) + kernels.get("kzgp_finish", 0.0)
+            print(json.dumps({
+                "call": what,
+                "n_blobs": n,
+                "reps": args.reps,
+                "ms_min": round(min(times) * 1e3, 4),
+                "ms_median": round(med * 1e3, 4),
+                "ms_max": round(max(times) * 1e3, 4),
+                "blobs_per_s_median": round(n / med, 2),
+                "kernel_ms_serialised": kernels,
+                "msm_kernels_ms": round(msm, 4),
+                "verify_kzg_mults_ms": vk.get("kzg_mults"),
+            }), flush=True)
+        for p in (blobs_d, cs_d, ps_d, out_d):
+            ctx.free(p)
+    k.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--sizes", default="1,6,192")
+    ap.add_argument("--sizes", default=None)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--prove", action="store_true",
+                    help="time commitment and blob-proof computation instead")
     args = ap.parse_args()
+    if args.sizes is None:
+        args.sizes = "1,6" if args.prove else "1,6,192"
 
     from lighthouse_amd import _native, kzg
 
     fx = json.loads((REPO / "tests" / "golden" / "kzg_fixtures.json").read_text())
     triples = make_triples(fx["test_setup"]["tau_seed"])
     ctx = _native.default_ctx()
+    if args.prove:
+        return prove_main(args, fx, triples, ctx, kzg)
     k = kzg.Kzg(bytes.fromhex(fx["test_setup"]["g2_tau"]), ctx=ctx)
     for n in [int(s) for s in args.sizes.split(",")]:
         ts = [triples[i % 3] for i in range(n)]

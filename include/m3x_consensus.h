@@ -53,7 +53,7 @@ int32_t m3x_abi_version(void);
  * 2 finalize, 3 bls_prepare, 4 bls_h2c, 5 bls_miller, 6 bls_reduce,
  * 7 bls_finish, 8 bls_agg, 9 kzg_challenge, 10 kzg_decomp, 11 kzg_eval,
  * 12 kzg_batch_r, 13 kzg_mults, 14 kzg_reduce, 15 kzg_finish,
- * 16 kzgp_quotient, 17 kzgp_msm, 18 kzgp_finish). */
+ * 16 kzgp_quotient, 17 kzgp_msm, 18 kzgp_finish, 19 bls_sigpair). */
 int32_t m3x_timing_enable(m3x_ctx *ctx, int32_t on);
 int32_t m3x_kernel_ms(m3x_ctx *ctx, int32_t kernel_id, double *ms,
                       uint64_t *launches);

@@ -1208,22 +1208,66 @@ __device__ __forceinline__ void f6_mul_v(fp6 &r, const fp6 &a) {
   r.c[1] = a.c[0];
   r.c[0] = t;
 }
-// schoolbook Fp6 multiply (9 fp2 muls) + v^3 = xi reduction
+// Karatsuba Fp6 multiply (6 fp2 muls vs 9 schoolbook) with the v^3 = xi
+// reduction folded in: v_i = a_i b_i,
+//   c0 = v0 + xi((a1+a2)(b1+b2) - v1 - v2)
+//   c1 = (a0+a1)(b0+b1) - v0 - v1 + xi v2
+//   c2 = (a0+a2)(b0+b2) - v0 - v2 + v1
+// r may alias a or b (r is written after the last read of either).
 __device__ __forceinline__ void f6_mul(fp6 &r, const fp6 &a, const fp6 &b) {
-  fp2 acc[5], t;
-  for (int i = 0; i < 5; i++) fp2_zero(acc[i]);
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      fp2_mul(t, a.c[i], b.c[j]);
-      fp2_add(acc[i + j], acc[i + j], t);
-    }
-  fp2_mul_xi(t, acc[3]);
-  fp2_add(r.c[0], acc[0], t);
-  fp2_mul_xi(t, acc[4]);
-  fp2_add(r.c[1], acc[1], t);
-  r.c[2] = acc[2];
+  fp2 v0, v1, v2, m12, m01, m02, s, t;
+  fp2_mul(v0, a.c[0], b.c[0]);
+  fp2_mul(v1, a.c[1], b.c[1]);
+  fp2_mul(v2, a.c[2], b.c[2]);
+  fp2_add(s, a.c[1], a.c[2]);
+  fp2_add(t, b.c[1], b.c[2]);
+  fp2_mul(m12, s, t);
+  fp2_add(s, a.c[0], a.c[1]);
+  fp2_add(t, b.c[0], b.c[1]);
+  fp2_mul(m01, s, t);
+  fp2_add(s, a.c[0], a.c[2]);
+  fp2_add(t, b.c[0], b.c[2]);
+  fp2_mul(m02, s, t);
+  fp2_sub(m12, m12, v1);
+  fp2_sub(m12, m12, v2);
+  fp2_mul_xi(m12, m12);
+  fp2_add(r.c[0], v0, m12);
+  fp2_sub(m01, m01, v0);
+  fp2_sub(m01, m01, v1);
+  fp2_mul_xi(t, v2);
+  fp2_add(r.c[1], m01, t);
+  fp2_sub(m02, m02, v0);
+  fp2_sub(m02, m02, v2);
+  fp2_add(r.c[2], m02, v1);
+}
+
+// Fp6 times the Fp2 scalar (k,0,0): 3 fp2 muls
+__device__ __forceinline__ void f6_mul_fp2(fp6 &r, const fp6 &a,
+                                           const fp2 &k) {
+  fp2_mul(r.c[0], a.c[0], k);
+  fp2_mul(r.c[1], a.c[1], k);
+  fp2_mul(r.c[2], a.c[2], k);
+}
+
+// Fp6 times the two-term operand (0,b1,b2): 5 fp2 muls,
+//   c0 = xi(a1b2 + a2b1), c1 = a0b1 + xi a2b2, c2 = a0b2 + a1b1
+// with a1b2 + a2b1 = (a1+a2)(b1+b2) - a1b1 - a2b2. r must not alias a.
+__device__ __forceinline__ void f6_mul_012s(fp6 &r, const fp6 &a,
+                                            const fp2 &b1, const fp2 &b2) {
+  fp2 v1, v2, s, t;
+  fp2_mul(v1, a.c[1], b1);
+  fp2_mul(v2, a.c[2], b2);
+  fp2_add(s, a.c[1], a.c[2]);
+  fp2_add(t, b1, b2);
+  fp2_mul(s, s, t);
+  fp2_sub(s, s, v1);
+  fp2_sub(s, s, v2);
+  fp2_mul_xi(r.c[0], s);
+  fp2_mul(s, a.c[0], b1);
+  fp2_mul_xi(t, v2);
+  fp2_add(r.c[1], s, t);
+  fp2_mul(s, a.c[0], b2);
+  fp2_add(r.c[2], s, v1);
 }
 
 __device__ __forceinline__ void f12_split(const fp12m &f, fp6 &A, fp6 &B) {
@@ -1244,8 +1288,9 @@ __device__ __forceinline__ void f12_join(fp12m &f, const fp6 &A,
   f12_set(f, 5, B.c[2]);
 }
 
-// r = a * b via the quadratic-over-cubic tower (3 Fp6 muls = 18 fp2 muls
-// vs 36 schoolbook); r may alias a or b (inputs are split out first).
+// r = a * b via the quadratic-over-cubic tower (3 Karatsuba Fp6 muls = 18
+// fp2 muls vs 36 schoolbook); r may alias a or b (inputs are split out
+// first).
 __device__ inline void f12_mul_nn(fp12m &r, const fp12m &a, const fp12m &b) {
   fp6 A1, B1, A2, B2, aa, bb, s1, s2, cross, even, t;
   f12_split(a, A1, B1);
@@ -1262,7 +1307,8 @@ __device__ inline void f12_mul_nn(fp12m &r, const fp12m &a, const fp12m &b) {
   f12_join(r, even, cross);
 }
 
-// r = a^2: complex squaring, 2 Fp6 muls = 12 fp2 muls; alias-safe.
+// r = a^2: complex squaring, 2 Karatsuba Fp6 muls = 12 fp2 muls;
+// alias-safe.
 __device__ inline void f12_sqr_nn(fp12m &r, const fp12m &a) {
   fp6 A, B, m1, t, u, even, odd;
   f12_split(a, A, B);
@@ -1278,23 +1324,27 @@ __device__ inline void f12_sqr_nn(fp12m &r, const fp12m &a) {
   f12_join(r, even, odd);
 }
 
-// r = f * (a0 + a3 w^3 + a5 w^5); r must not alias f (sparse: 18 fp2 muls)
+// r = f * (a0 + a3 w^3 + a5 w^5), 14 fp2 muls (18 coefficient-wise). In
+// the tower view the line is A_l = (a0,0,0), B_l = (0,a3,a5), so
+//   f*l = (A A_l + v B B_l) + w((A+B)(A_l+B_l) - A A_l - B B_l)
+// with A A_l a scalar product (3), B B_l a two-term product (5) and only
+// the cross term dense (6). r may alias f (f is split out first).
 __device__ inline void f12_line_nn(fp12m &r, const fp12m &f, const fp2 &a0,
                                    const fp2 &a3, const fp2 &a5) {
-  for (int k = 0; k < 6; k++) {
-    fp2 acc, fk, t;
-    f12_get(f, k, fk);
-    fp2_mul(acc, fk, a0);
-    f12_get(f, (k + 3) % 6, fk);
-    fp2_mul(t, fk, a3);
-    if (k < 3) fp2_mul_xi(t, t);
-    fp2_add(acc, acc, t);
-    f12_get(f, (k + 1) % 6, fk); // (k - 5) mod 6
-    fp2_mul(t, fk, a5);
-    if (k < 5) fp2_mul_xi(t, t);
-    fp2_add(acc, acc, t);
-    f12_set(r, k, acc);
-  }
+  fp6 A, B, aa, bb, s, l, cross, even;
+  f12_split(f, A, B);
+  f6_mul_fp2(aa, A, a0);
+  f6_mul_012s(bb, B, a3, a5);
+  f6_add(s, A, B);
+  l.c[0] = a0;
+  l.c[1] = a3;
+  l.c[2] = a5;
+  f6_mul(cross, s, l);
+  f6_sub(cross, cross, aa);
+  f6_sub(cross, cross, bb);
+  f6_mul_v(s, bb);
+  f6_add(even, aa, s);
+  f12_join(r, even, cross);
 }
 
 // f^(p^6): odd w-coefficients negate (in place; validated by the generator)
@@ -1321,101 +1371,133 @@ __device__ inline bool f12_is_one(const fp12m &a) {
 
 // ---------------------------------------------------------------- pairing ---
 
-// out = miller(P, Q) (already conjugated for x<0); tmp is scratch; out and
-// tmp must be distinct. Inversion-free Jacobian loop on the twist with
-// sparse lines (formulas validated against the Python reference).
-__device__ inline void miller_raw(fp12m &out, fp12m &tmp, const g1j &Pj,
-                                  const g2j &Qj) {
-  f12_one(out);
-  if (fp_is_zero(Pj.z) || fp2_is_zero(Qj.z)) return; // e(O,.) = e(.,O) = 1
-  g2j T = Qj;
-  // BOTH points stay JACOBIAN (no inversions anywhere; validated in
-  // Python). P side: lines scaled by the Fp-subfield factor Zp^3 — a0
-  // uses Yp directly, a3's xi^-1 absorbs Zp^3, a5 uses Xp*Zp. Q side:
-  // addition lines scaled by the further subfield-norm factor Zq^3 via
-  // H* = X*Zq^2 - Xq*Z^2 (= H*Zq^2), M* = Y*Zq^3 - Yq*Z^3 (= M*Zq^3),
-  // with a0/a3 consuming H*Zq. xi^-1 = (1-u)/2 is a constant.
-  fp2 xi_inv, xi_inv_zp3, zq2, zq3;
-  FP_LOAD_C(xi_inv.c0, FP_TWO_INV);
-  fp_neg(xi_inv.c1, xi_inv.c0);
-  fp2_sqr(zq2, Qj.z);
-  fp2_mul(zq3, zq2, Qj.z);
-  fp zp2, zp3, xpzp;
+// Per-pair constants of the inversion-free Miller loop. BOTH points stay
+// JACOBIAN (no inversions anywhere; validated in Python). P side: lines
+// are scaled by the Fp-subfield factor Zp^3 — a0 uses Yp directly, a3
+// takes Zp^3, a5 uses Xp*Zp. Q side: addition lines carry the further
+// subfield-norm factor Zq^3 via H* = X*Zq^2 - Xq*Z^2 (= H*Zq^2),
+// M* = Y*Zq^3 - Yq*Z^3 (= M*Zq^3), with a0/a3 consuming H*Zq.
+// Every line is additionally scaled by xi (instead of carrying xi^-1 in
+// a3 and a5): a nonzero Fp2 factor lies in the Fp6 subfield and dies in
+// the easy part of the final exponentiation, and xi*a0 is adds only.
+struct miller_pre {
+  fp xp, yp, zp3; // Xp*Zp, Yp, Zp^3
+  fp2 zq2, zq3;   // Zq^2, Zq^3
+};
+
+__device__ inline void miller_precompute(miller_pre &c, const g1j &Pj,
+                                         const g2j &Qj) {
+  fp zp2;
   fp_sqr(zp2, Pj.z);
-  fp_mul(zp3, zp2, Pj.z);
-  fp_mul(xpzp, Pj.x, Pj.z);
-  fp2_mul_fp(xi_inv_zp3, xi_inv, zp3);
-  fp12m *cur = &out, *tm = &tmp;
-  fp xp = xpzp, yp = Pj.y; // a5 gets Xp*Zp, a0 gets Yp
-  for (int i = 62; i >= 0; i--) {
-    f12_sqr_nn(*tm, *cur);
-    {
-      fp12m *sw = cur;
-      cur = tm;
-      tm = sw;
-    }
-    // doubling line from Jacobian T:
-    // a0 = 2*Y*Z^3*yp ; a3 = (3X^3 - 2Y^2)*xi_inv ; a5 = -3X^2*Z^2*xp*xi_inv
-    {
-      fp2 X2, Y2, Z2, Z3, a0, a3, a5, t, t2;
-      fp2_sqr(X2, T.x);
-      fp2_sqr(Y2, T.y);
-      fp2_sqr(Z2, T.z);
-      fp2_mul(Z3, Z2, T.z);
-      fp2_mul(t, T.y, Z3);
-      fp2_dbl(t, t);
-      fp2_mul_fp(a0, t, yp);
-      fp2_mul(t, X2, T.x);
-      fp2_mul_small(t, t, 3);
-      fp2_dbl(t2, Y2);
-      fp2_sub(t, t, t2);
-      fp2_mul(a3, t, xi_inv_zp3);
-      fp2_mul(t, X2, Z2);
-      fp2_mul_small(t, t, 3);
-      fp2_mul_fp(t, t, xp);
-      fp2_neg(t, t);
-      fp2_mul(a5, t, xi_inv);
-      f12_line_nn(*tm, *cur, a0, a3, a5);
-      {
-        fp12m *sw = cur;
-        cur = tm;
-        tm = sw;
-      }
-      g2j_dbl(T, T);
-    }
+  fp_mul(c.zp3, zp2, Pj.z);
+  fp_mul(c.xp, Pj.x, Pj.z);
+  c.yp = Pj.y;
+  fp2_sqr(c.zq2, Qj.z);
+  fp2_mul(c.zq3, c.zq2, Qj.z);
+}
+
+// One doubling step: the tangent line at T evaluated at P, and T <- 2T.
+// The line and the doubling (dbl-2009-l) share A = X^2, B = Y^2, E = 3A
+// and Z3 = 2YZ:
+//   a0 = xi * Z3*Z^2 * yp ; a3 = (E*X - 2B) * zp3 ; a5 = -E*Z^2 * xp
+// (33 Fp mults against 28 + 16 for separate line and g2j_dbl).
+__device__ inline void miller_dbl_step(g2j &T, fp2 &a0, fp2 &a3, fp2 &a5,
+                                       const miller_pre &c) {
+  fp2 A, B, C, D, E, F, Z2, Z3, t, t2;
+  fp2_sqr(A, T.x);
+  fp2_sqr(B, T.y);
+  fp2_sqr(Z2, T.z);
+  fp2_dbl(E, A);
+  fp2_add(E, E, A);
+  fp2_mul(t, T.y, T.z);
+  fp2_dbl(Z3, t);
+  fp2_mul(t, Z3, Z2);
+  fp2_mul_fp(t, t, c.yp);
+  fp2_mul_xi(a0, t);
+  fp2_mul(t, E, T.x);
+  fp2_dbl(t2, B);
+  fp2_sub(t, t, t2);
+  fp2_mul_fp(a3, t, c.zp3);
+  fp2_mul(t, E, Z2);
+  fp2_mul_fp(t, t, c.xp);
+  fp2_neg(a5, t);
+  fp2_sqr(C, B);
+  fp2_add(D, T.x, B);
+  fp2_sqr(D, D);
+  fp2_sub(D, D, A);
+  fp2_sub(D, D, C);
+  fp2_dbl(D, D);
+  fp2_sqr(F, E);
+  fp2_sub(F, F, D);
+  fp2_sub(F, F, D);
+  fp2_sub(t, D, F);
+  fp2_mul(t, E, t);
+  fp2_dbl(C, C);
+  fp2_dbl(C, C);
+  fp2_dbl(C, C);
+  fp2_sub(T.y, t, C);
+  T.x = F;
+  T.z = Z3;
+}
+
+// One addition step: the line through T and Q (both Jacobian) evaluated
+// at P, scaled by Zq^3 and xi, and T <- T + Q:
+//   a0 = xi * Z^3*H*Zq * yp ; a3 = (M**X - Y*H*Zq) * zp3 ;
+//   a5 = -M**Z^2 * xp
+__device__ inline void miller_add_step(g2j &T, fp2 &a0, fp2 &a3, fp2 &a5,
+                                       const g2j &Qj, const miller_pre &c) {
+  fp2 Z2, Z3, Hs, Ms, HZq, t, t2;
+  fp2_sqr(Z2, T.z);
+  fp2_mul(Z3, Z2, T.z);
+  fp2_mul(t, T.x, c.zq2);
+  fp2_mul(t2, Qj.x, Z2);
+  fp2_sub(Hs, t, t2); // H* = H*Zq^2
+  fp2_mul(t, T.y, c.zq3);
+  fp2_mul(t2, Qj.y, Z3);
+  fp2_sub(Ms, t, t2); // M* = M*Zq^3
+  fp2_mul(HZq, Hs, Qj.z);
+  fp2_mul(t, Z3, HZq);
+  fp2_mul_fp(t, t, c.yp);
+  fp2_mul_xi(a0, t);
+  fp2_mul(t, Ms, T.x);
+  fp2_mul(t2, T.y, HZq);
+  fp2_sub(t, t, t2);
+  fp2_mul_fp(a3, t, c.zp3);
+  fp2_mul(t, Ms, Z2);
+  fp2_mul_fp(t, t, c.xp);
+  fp2_neg(a5, t);
+  g2j_add(T, T, Qj);
+}
+
+// f <- f^2 * line for Miller iterations hi..lo of |x|: the shared body of
+// miller_raw and miller_half. The tower square and the line product split
+// their input out before writing, so f is updated in place and the loop
+// needs no second Fp12 buffer.
+__device__ inline void miller_iters(fp12m &f, g2j &T, const g2j &Qj,
+                                    const miller_pre &c, int hi, int lo) {
+  for (int i = hi; i >= lo; i--) {
+    fp2 a0, a3, a5;
+    f12_sqr_nn(f, f);
+    miller_dbl_step(T, a0, a3, a5, c);
+    f12_line_nn(f, f, a0, a3, a5);
     if ((BLS_X_ABS >> i) & 1) {
-      // addition line through T (jac) and Q (jac), scaled by Zq^3
-      fp2 Z2, Z3, Hs, Ms, HZq, a0, a3, a5, t, t2;
-      fp2_sqr(Z2, T.z);
-      fp2_mul(Z3, Z2, T.z);
-      fp2_mul(t, T.x, zq2);
-      fp2_mul(t2, Qj.x, Z2);
-      fp2_sub(Hs, t, t2); // H* = H*Zq^2
-      fp2_mul(t, T.y, zq3);
-      fp2_mul(t2, Qj.y, Z3);
-      fp2_sub(Ms, t, t2); // M* = M*Zq^3
-      fp2_mul(HZq, Hs, Qj.z);
-      fp2_mul(t, Z3, HZq);
-      fp2_mul_fp(a0, t, yp);
-      fp2_mul(t, Ms, T.x);
-      fp2_mul(t2, T.y, HZq);
-      fp2_sub(t, t, t2);
-      fp2_mul(a3, t, xi_inv_zp3);
-      fp2_mul(t, Ms, Z2);
-      fp2_mul_fp(t, t, xp);
-      fp2_neg(t, t);
-      fp2_mul(a5, t, xi_inv);
-      f12_line_nn(*tm, *cur, a0, a3, a5);
-      {
-        fp12m *sw = cur;
-        cur = tm;
-        tm = sw;
-      }
-      g2j_add(T, T, Qj);
+      miller_add_step(T, a0, a3, a5, Qj, c);
+      f12_line_nn(f, f, a0, a3, a5);
     }
   }
-  f12_conj6_ip(*cur); // x < 0
-  if (cur != &out) f12_copy(out, *cur);
+}
+
+// out = miller(P, Q) (already conjugated for x<0). Inversion-free Jacobian
+// loop on the twist with sparse lines (formulas validated against the
+// Python reference, tests/test_pairing_formulas_ref.py).
+__device__ inline void miller_raw(fp12m &out, const g1j &Pj, const g2j &Qj) {
+  f12_one(out);
+  if (fp_is_zero(Pj.z) || fp2_is_zero(Qj.z)) return; // e(O,.) = e(.,O) = 1
+  miller_pre c;
+  miller_precompute(c, Pj, Qj);
+  g2j T = Qj;
+  miller_iters(out, T, Qj, c, 62, 0);
+  f12_conj6_ip(out); // x < 0
 }
 
 
@@ -1434,19 +1516,9 @@ __device__ inline void miller_half(fp12m &out, const g1j &Pj, const g2j &Qj,
                                    int role) {
   f12_one(out);
   if (fp_is_zero(Pj.z) || fp2_is_zero(Qj.z)) return;
-  fp2 xi_inv, xi_inv_zp3, zq2, zq3;
-  FP_LOAD_C(xi_inv.c0, FP_TWO_INV);
-  fp_neg(xi_inv.c1, xi_inv.c0);
-  fp2_sqr(zq2, Qj.z);
-  fp2_mul(zq3, zq2, Qj.z);
-  fp zp2, zp3, xp, yp;
-  fp_sqr(zp2, Pj.z);
-  fp_mul(zp3, zp2, Pj.z);
-  fp_mul(xp, Pj.x, Pj.z);
-  yp = Pj.y;
-  fp2_mul_fp(xi_inv_zp3, xi_inv, zp3);
+  miller_pre c;
+  miller_precompute(c, Pj, Qj);
   g2j T = Qj;
-  fp12m tmp;
   int lo = role == 0 ? 32 : 0;
   int hi = role == 0 ? 62 : 31;
   if (role == 1) {
@@ -1457,85 +1529,13 @@ __device__ inline void miller_half(fp12m &out, const g1j &Pj, const g2j &Qj,
       if ((BLS_X_ABS >> i) & 1) g2j_add(T, T, Qj);
     }
   }
-  fp12m *cur = &out, *tm = &tmp;
-  for (int i = hi; i >= lo; i--) {
-    f12_sqr_nn(*tm, *cur);
-    {
-      fp12m *sw = cur;
-      cur = tm;
-      tm = sw;
-    }
-    {
-      fp2 X2, Y2, Z2, Z3, a0, a3, a5, t, t2;
-      fp2_sqr(X2, T.x);
-      fp2_sqr(Y2, T.y);
-      fp2_sqr(Z2, T.z);
-      fp2_mul(Z3, Z2, T.z);
-      fp2_mul(t, T.y, Z3);
-      fp2_dbl(t, t);
-      fp2_mul_fp(a0, t, yp);
-      fp2_mul(t, X2, T.x);
-      fp2_mul_small(t, t, 3);
-      fp2_dbl(t2, Y2);
-      fp2_sub(t, t, t2);
-      fp2_mul(a3, t, xi_inv_zp3);
-      fp2_mul(t, X2, Z2);
-      fp2_mul_small(t, t, 3);
-      fp2_mul_fp(t, t, xp);
-      fp2_neg(t, t);
-      fp2_mul(a5, t, xi_inv);
-      f12_line_nn(*tm, *cur, a0, a3, a5);
-      {
-        fp12m *sw = cur;
-        cur = tm;
-        tm = sw;
-      }
-      g2j_dbl(T, T);
-    }
-    if ((BLS_X_ABS >> i) & 1) {
-      fp2 Z2, Z3, Hs, Ms, HZq, a0, a3, a5, t, t2;
-      fp2_sqr(Z2, T.z);
-      fp2_mul(Z3, Z2, T.z);
-      fp2_mul(t, T.x, zq2);
-      fp2_mul(t2, Qj.x, Z2);
-      fp2_sub(Hs, t, t2);
-      fp2_mul(t, T.y, zq3);
-      fp2_mul(t2, Qj.y, Z3);
-      fp2_sub(Ms, t, t2);
-      fp2_mul(HZq, Hs, Qj.z);
-      fp2_mul(t, Z3, HZq);
-      fp2_mul_fp(a0, t, yp);
-      fp2_mul(t, Ms, T.x);
-      fp2_mul(t2, T.y, HZq);
-      fp2_sub(t, t, t2);
-      fp2_mul(a3, t, xi_inv_zp3);
-      fp2_mul(t, Ms, Z2);
-      fp2_mul_fp(t, t, xp);
-      fp2_neg(t, t);
-      fp2_mul(a5, t, xi_inv);
-      f12_line_nn(*tm, *cur, a0, a3, a5);
-      {
-        fp12m *sw = cur;
-        cur = tm;
-        tm = sw;
-      }
-      g2j_add(T, T, Qj);
-    }
-  }
+  miller_iters(out, T, Qj, c, hi, lo);
   if (role == 0) {
     // f_hi^(2^32): the tail squarings that align the high half with the
     // 32 low-half iterations it skipped
-    for (int k = 0; k < 32; k++) {
-      f12_sqr_nn(*tm, *cur);
-      {
-        fp12m *sw = cur;
-        cur = tm;
-        tm = sw;
-      }
-    }
+    for (int k = 0; k < 32; k++) f12_sqr_nn(out, out);
   }
-  f12_conj6_ip(*cur); // x < 0 (conj6 distributes over the half product)
-  if (cur != &out) f12_copy(out, *cur);
+  f12_conj6_ip(out); // x < 0 (conj6 distributes over the half product)
 }
 
 

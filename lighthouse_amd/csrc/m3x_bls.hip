@@ -45,6 +45,7 @@ struct BlsWork {
   g2j *sig_sum;    // [1]
   fp12m *gt_stage; // [256] stage-1 partial products
   fp12m *gt_parts; // [1]
+  fp12m *sig_gt;   // [1] miller(-g1, sig_sum), written by the side stream
   int *verdict;    // [1]
 };
 
@@ -96,15 +97,18 @@ __global__ void k_bls_scan_agg(const uint32_t *__restrict__ offs, uint64_t n,
   }
 }
 
+// grid cap of k_bls_aggregate_w (its blocks stride over the k>1 sets)
+constexpr uint32_t kAggMaxBlocks = 32768;
+
 // one WAVE per k>1 set: each lane partial-sums a strided slice of the
 // set's pubkeys in Jacobian form, then an LDS tree reduce (6 levels)
 __global__ __launch_bounds__(64, 1) void k_bls_aggregate_w(
     const uint8_t *__restrict__ pks, const uint32_t *__restrict__ offs,
     BlsWork w) {
   __shared__ g1j lds[64];
-  // grid-stride over the aggregate list: the grid is FIXED (8192 blocks)
-  // so a k=1-only workload costs ~nothing — launching n blocks of
-  // early-exits measured 183 ms at n=1M (rocprof r02)
+  // grid-stride over the aggregate list: the grid is CAPPED (at
+  // kAggMaxBlocks) so a k=1-only workload costs ~nothing — launching n
+  // blocks of early-exits measured 183 ms at n=1M (rocprof r02)
   for (uint32_t b = blockIdx.x; b < *w.agg_count; b += gridDim.x) {
   uint64_t set = w.agg_idx[b];
   uint32_t k0 = offs[set], k1 = offs[set + 1];
@@ -434,9 +438,9 @@ __global__ __launch_bounds__(64, 1) void k_bls_miller(uint64_t n, BlsWork w) {
   // at 4 blocks — reverted; measured round 2.)
   uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  fp12m f, tmp;
+  fp12m f;
   if (*w.fail == 0)
-    miller_raw(f, tmp, w.p_scaled[i], w.h2c[i]);
+    miller_raw(f, w.p_scaled[i], w.h2c[i]);
   else
     f12_one(f);
   w.fparts[i] = f;
@@ -465,49 +469,69 @@ __attribute__((amdgpu_waves_per_eu(2))) void k_bls_miller_split(
   w.fparts[lane] = f;
 }
 
+// Threads per block of the two batch reductions. 128 keeps the LDS of one
+// GT block (128 x 576 B) plus one signature block (128 x 288 B) at 108 KiB,
+// under the CU's 160 KiB, so blocks of the two chains — which run on two
+// streams — can share a CU; a block is two waves, so the pair also fits on
+// separate SIMDs whatever their register budgets.
+constexpr int kReduceThreads = 128;
+// Stage-1 block cap (= the capacity of the gt_stage / sig_stage buffers).
+constexpr uint32_t kReduceMaxBlocks = 256;
+
 // two-stage GT-product reduction: each block folds its contiguous span of
 // per-set miller values (thread-strided local products, then an LDS tree)
 // into one output element; a second 1-block launch folds the partials.
-__global__ __launch_bounds__(256) void k_bls_reduce_gt(
+// A thread starts from its first element (no multiply by one); only a
+// thread with no element contributes one.
+__global__ __launch_bounds__(kReduceThreads) void k_bls_reduce_gt(
     const fp12m *__restrict__ in, uint64_t n, fp12m *__restrict__ out) {
-  __shared__ fp12m lds[256];
+  __shared__ fp12m lds[kReduceThreads];
   uint64_t per = (n + gridDim.x - 1) / gridDim.x;
   uint64_t lo = (uint64_t)blockIdx.x * per;
   uint64_t hi = lo + per < n ? lo + per : n;
-  fp12m local, t;
-  f12_one(local);
-  for (uint64_t i = lo + threadIdx.x; i < hi; i += 256) {
-    f12_mul_nn(t, local, in[i]);
-    f12_copy(local, t);
+  fp12m local;
+  uint64_t i = lo + threadIdx.x;
+  if (i < hi) {
+    f12_copy(local, in[i]);
+    for (i += kReduceThreads; i < hi; i += kReduceThreads)
+      f12_mul_nn(local, local, in[i]);
+  } else {
+    f12_one(local);
   }
   lds[threadIdx.x] = local;
   __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
+  for (int s = kReduceThreads / 2; s > 0; s >>= 1) {
     if ((int)threadIdx.x < s) {
-      f12_mul_nn(t, lds[threadIdx.x], lds[threadIdx.x + s]);
-      f12_copy(lds[threadIdx.x], t);
+      f12_mul_nn(local, lds[threadIdx.x], lds[threadIdx.x + s]);
+      f12_copy(lds[threadIdx.x], local);
     }
     __syncthreads();
   }
   if (threadIdx.x == 0) out[blockIdx.x] = lds[0];
 }
 
-// two-stage sum of r_i*sigma_i, same shape
-__global__ __launch_bounds__(256) void k_bls_reduce_sig(
+// two-stage sum of r_i*sigma_i, same shape (a thread with no element
+// contributes infinity)
+__global__ __launch_bounds__(kReduceThreads) void k_bls_reduce_sig(
     const g2j *__restrict__ in, uint64_t n, g2j *__restrict__ out) {
-  __shared__ g2j lds[256];
+  __shared__ g2j lds[kReduceThreads];
   uint64_t per = (n + gridDim.x - 1) / gridDim.x;
   uint64_t lo = (uint64_t)blockIdx.x * per;
   uint64_t hi = lo + per < n ? lo + per : n;
   g2j local;
-  fp2_zero(local.x);
-  fp2_zero(local.y);
-  fp2_zero(local.z);
-  for (uint64_t i = lo + threadIdx.x; i < hi; i += 256)
-    g2j_add(local, local, in[i]);
+  uint64_t i = lo + threadIdx.x;
+  if (i < hi) {
+    local = in[i];
+    for (i += kReduceThreads; i < hi; i += kReduceThreads)
+      g2j_add(local, local, in[i]);
+  } else {
+    fp2_zero(local.x);
+    fp2_zero(local.y);
+    fp2_zero(local.z);
+  }
   lds[threadIdx.x] = local;
   __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
+  for (int s = kReduceThreads / 2; s > 0; s >>= 1) {
     if ((int)threadIdx.x < s) {
       g2j t;
       g2j_add(t, lds[threadIdx.x], lds[threadIdx.x + s]);
@@ -518,16 +542,17 @@ __global__ __launch_bounds__(256) void k_bls_reduce_sig(
   if (threadIdx.x == 0) out[blockIdx.x] = lds[0];
 }
 
-// final: f_total *= miller(-g1, sig_sum); final_exp; compare to one.
-// One wave, cooperative fp12 ops in LDS (the per-batch serial tail: the
-// 36 coefficient products of each Fp12 multiply fan across lanes).
-__global__ __launch_bounds__(64) void k_bls_finish(BlsWork w) {
-  __shared__ fp12m sh[7];
+// signature pair: sig_gt = miller(-g1, sig_sum), one cooperative wave.
+// Runs on the side stream next to the GT reduction (it needs nothing from
+// the per-set Miller kernel). A failed batch or an infinite signature sum
+// gives one: e(., O) = 1.
+__global__ __launch_bounds__(64) void k_bls_sigpair(BlsWork w) {
+  __shared__ fp12m f;
   __shared__ f12w_ws ws;
   __shared__ miller_ws mws;
   int lane = threadIdx.x;
   if (*w.fail) {
-    if (lane == 0) *w.verdict = 0;
+    if (lane == 0) f12_one(w.sig_gt[0]);
     return;
   }
   g1j ng1;
@@ -538,10 +563,26 @@ __global__ __launch_bounds__(64) void k_bls_finish(BlsWork w) {
     fp_neg(ng1.y, g.y);
     fp_one(ng1.z);
   }
-  if (lane == 0) f12_copy(sh[0], w.gt_parts[0]);
-  f12w_sync();
   // sig_sum stays Jacobian: the Q-Jacobian Miller loop needs no inversion
-  miller_w(sh[1], ng1, w.sig_sum[0], ws, mws, lane);
+  // (and returns one for an infinite Q)
+  miller_w(f, ng1, w.sig_sum[0], ws, mws, lane);
+  f12w_sync();
+  f12_copy_w(w.sig_gt[0], f, lane);
+}
+
+// final: f_total = gt_parts * sig_gt; final_exp; compare to one.
+// One wave, cooperative fp12 ops in LDS (the per-batch serial tail: the
+// 36 coefficient products of each Fp12 multiply fan across lanes).
+__global__ __launch_bounds__(64) void k_bls_finish(BlsWork w) {
+  __shared__ fp12m sh[7];
+  __shared__ f12w_ws ws;
+  int lane = threadIdx.x;
+  if (*w.fail) {
+    if (lane == 0) *w.verdict = 0;
+    return;
+  }
+  f12_copy_w(sh[0], w.gt_parts[0], lane);
+  f12_copy_w(sh[1], w.sig_gt[0], lane);
   f12_mul_w(sh[1], sh[0], sh[1], ws, lane); // f_total
   final_exp_w(sh[2], sh[1], &sh[3], ws, lane);
   if (lane == 0) *w.verdict = f12_is_one(sh[2]) ? 1 : 0;
@@ -863,10 +904,11 @@ int run_verify(m3x_ctx *ctx, const void *msgs_dev, const void *sigs_dev,
   uint64_t off_sa = bytes; bytes += align(n * sizeof(g2j));
   uint64_t off_f = bytes; bytes += align(2 * n * sizeof(fp12m)); // split miller: 2n partials
   uint64_t off_fail = bytes; bytes += 256;
-  uint64_t off_sig_stage = bytes; bytes += align(256 * sizeof(g2j));
+  uint64_t off_sig_stage = bytes; bytes += align(kReduceMaxBlocks * sizeof(g2j));
   uint64_t off_sum = bytes; bytes += align(sizeof(g2j));
-  uint64_t off_gt_stage = bytes; bytes += align(256 * sizeof(fp12m));
+  uint64_t off_gt_stage = bytes; bytes += align(kReduceMaxBlocks * sizeof(fp12m));
   uint64_t off_gt = bytes; bytes += align(sizeof(fp12m));
+  uint64_t off_sig_gt = bytes; bytes += align(sizeof(fp12m));
   uint64_t off_v = bytes; bytes += 256;
   int rc = m3x::ensure_scratch(ctx, &ctx->scratch_a, &ctx->scratch_a_bytes,
                                bytes);
@@ -887,6 +929,7 @@ int run_verify(m3x_ctx *ctx, const void *msgs_dev, const void *sigs_dev,
   w.sig_sum = reinterpret_cast<g2j *>(base + off_sum);
   w.gt_stage = reinterpret_cast<fp12m *>(base + off_gt_stage);
   w.gt_parts = reinterpret_cast<fp12m *>(base + off_gt);
+  w.sig_gt = reinterpret_cast<fp12m *>(base + off_sig_gt);
   w.verdict = reinterpret_cast<int *>(base + off_v);
   M3X_HIP_CHECK(hipMemsetAsync(w.fail, 0, 4, ctx->stream));
   M3X_HIP_CHECK(hipMemsetAsync(w.agg_count, 0, 4, ctx->stream));
@@ -895,7 +938,7 @@ int run_verify(m3x_ctx *ctx, const void *msgs_dev, const void *sigs_dev,
   hipLaunchKernelGGL(k_bls_scan_agg, dim3(blocks), dim3(64), 0, ctx->stream,
                      (const uint32_t *)offs_dev, n, w);
   {
-    uint32_t agg_blocks = n < 32768 ? (uint32_t)n : 32768;
+    uint32_t agg_blocks = n < kAggMaxBlocks ? (uint32_t)n : kAggMaxBlocks;
     hipLaunchKernelGGL(k_bls_aggregate_w, dim3(agg_blocks), dim3(64), 0,
                        ctx->stream, (const uint8_t *)pks_dev,
                        (const uint32_t *)offs_dev, w);
@@ -950,12 +993,11 @@ int run_verify(m3x_ctx *ctx, const void *msgs_dev, const void *sigs_dev,
   uint64_t small_thresh = 2048; // measured crossover (tmp_bench/c4probe)
   if (const char *e = getenv("M3X_SMALL_MILLER")) small_thresh = strtoull(e, nullptr, 10);
   uint64_t n_parts = n; // fp12 partials feeding the GT reduce
-  static int use_split = -1;
-  if (use_split < 0) {
-    const char *e = getenv("M3X_MILLER_SPLIT");
-    use_split = (e && e[0] == '1') ? 1 : 0; // measured SLOWER at C2 (57
-    // vs 44 ms: the 256-VGPR cap spills more than co-residency saves)
-  }
+  // read per call (as M3X_SMALL_MILLER is) so both forms are testable
+  // in-process; measured SLOWER at C2 (57 vs 44 ms: the 256-VGPR cap
+  // spills more than co-residency saves)
+  const char *split_env = getenv("M3X_MILLER_SPLIT");
+  bool use_split = split_env && split_env[0] == '1';
   if (n <= small_thresh) {
     hipLaunchKernelGGL(k_bls_miller_small, dim3((uint32_t)n), dim3(64), 0,
                        ctx->stream, n, w);
@@ -970,19 +1012,45 @@ int run_verify(m3x_ctx *ctx, const void *msgs_dev, const void *sigs_dev,
   }
   m3x::time_end(ctx, M3X_K_BLS_MILLER);
   DBG_STEP(ctx, "miller");
-  uint32_t rblocks = (uint32_t)((n_parts + 255) / 256);
-  if (rblocks > 256) rblocks = 256;
+  // The batch tail is two independent chains:
+  //   main stream : reduce_gt x2                      -> gt_parts
+  //   stream3     : reduce_sig x2 -> sigpair (Miller) -> sig_gt
+  // joined by k_bls_finish. The signature chain reads only rsig (complete
+  // once the prepare kernels are) and is the sole writer of sig_stage,
+  // sig_sum and sig_gt; nothing else touches them until k_bls_finish,
+  // which waits on ev_pipe[1]. It is released after the per-set Miller
+  // kernel. Releasing it right after the prepare kernels was measured and
+  // gains nothing: prepare, not h2c, is what the Miller kernel waits for,
+  // so the chain then starts together with that kernel, which owns every
+  // SIMD's register file — reduce_sig starves and the Miller kernel grows
+  // by what the tail saves ("Tail placement").
+  // The next call on this context cannot overtake the side
+  // stream: the verdict read-back below synchronises the main stream,
+  // whose k_bls_finish has by then waited for the side stream's last
+  // kernel.
+  M3X_HIP_CHECK(hipEventRecord(ctx->ev_pipe[0], ctx->stream));
+  M3X_HIP_CHECK(hipStreamWaitEvent(ctx->stream3, ctx->ev_pipe[0], 0));
+  uint32_t sblocks = (uint32_t)((n + kReduceThreads - 1) / kReduceThreads);
+  if (sblocks > kReduceMaxBlocks) sblocks = kReduceMaxBlocks;
+  m3x::time_begin_s(ctx, M3X_K_BLS_SIGPAIR, ctx->stream3);
+  hipLaunchKernelGGL(k_bls_reduce_sig, dim3(sblocks), dim3(kReduceThreads), 0,
+                     ctx->stream3, w.rsig, n, w.sig_stage);
+  hipLaunchKernelGGL(k_bls_reduce_sig, dim3(1), dim3(kReduceThreads), 0,
+                     ctx->stream3, w.sig_stage, (uint64_t)sblocks, w.sig_sum);
+  hipLaunchKernelGGL(k_bls_sigpair, dim3(1), dim3(64), 0, ctx->stream3, w);
+  m3x::time_end_s(ctx, M3X_K_BLS_SIGPAIR, ctx->stream3);
+  M3X_HIP_CHECK(hipEventRecord(ctx->ev_pipe[1], ctx->stream3));
+  uint32_t rblocks =
+      (uint32_t)((n_parts + kReduceThreads - 1) / kReduceThreads);
+  if (rblocks > kReduceMaxBlocks) rblocks = kReduceMaxBlocks;
   m3x::time_begin(ctx, M3X_K_BLS_REDUCE);
-  hipLaunchKernelGGL(k_bls_reduce_gt, dim3(rblocks), dim3(256), 0,
+  hipLaunchKernelGGL(k_bls_reduce_gt, dim3(rblocks), dim3(kReduceThreads), 0,
                      ctx->stream, w.fparts, n_parts, w.gt_stage);
-  hipLaunchKernelGGL(k_bls_reduce_gt, dim3(1), dim3(256), 0, ctx->stream,
-                     w.gt_stage, (uint64_t)rblocks, w.gt_parts);
-  hipLaunchKernelGGL(k_bls_reduce_sig, dim3(rblocks), dim3(256), 0,
-                     ctx->stream, w.rsig, n, w.sig_stage);
-  hipLaunchKernelGGL(k_bls_reduce_sig, dim3(1), dim3(256), 0, ctx->stream,
-                     w.sig_stage, (uint64_t)rblocks, w.sig_sum);
+  hipLaunchKernelGGL(k_bls_reduce_gt, dim3(1), dim3(kReduceThreads), 0,
+                     ctx->stream, w.gt_stage, (uint64_t)rblocks, w.gt_parts);
   m3x::time_end(ctx, M3X_K_BLS_REDUCE);
   DBG_STEP(ctx, "reduce");
+  M3X_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->ev_pipe[1], 0));
   m3x::time_begin(ctx, M3X_K_BLS_FINISH);
   hipLaunchKernelGGL(k_bls_finish, dim3(1), dim3(64), 0, ctx->stream, w);
   m3x::time_end(ctx, M3X_K_BLS_FINISH);

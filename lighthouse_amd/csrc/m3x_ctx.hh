@@ -25,7 +25,8 @@ enum m3x_kernel_id {
   M3X_K_KZGP_QUOTIENT = 16, // proof quotient in evaluation form
   M3X_K_KZGP_MSM = 17,      // fixed-base MSM: table look-ups + block sums
   M3X_K_KZGP_FINISH = 18,   // last G1 sum + compression
-  M3X_K_COUNT = 19
+  M3X_K_BLS_SIGPAIR = 19,   // signature sum + its Miller loop (stream3)
+  M3X_K_COUNT = 20
 };
 
 struct m3x_ctx {

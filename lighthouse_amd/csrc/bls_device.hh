@@ -568,11 +568,15 @@ __device__ __forceinline__ bool g1j_is_inf(const g1j &p) {
   return fp_is_zero(p.z);
 }
 
+__device__ __forceinline__ void g1j_set_inf(g1j &p) {
+  fp_zero(p.x);
+  fp_zero(p.y);
+  fp_zero(p.z);
+}
+
 __device__ inline void g1j_from_aff(g1j &r, const g1a &a) {
   if (a.inf) {
-    fp_zero(r.x);
-    fp_zero(r.y);
-    fp_zero(r.z);
+    g1j_set_inf(r);
     return;
   }
   r.x = a.x;
@@ -649,9 +653,7 @@ __device__ inline void g1j_add(g1j &r, const g1j &p, const g1j &q) {
       g1j_dbl(r, p);
       return;
     }
-    fp_zero(r.x);
-    fp_zero(r.y);
-    fp_zero(r.z);
+    g1j_set_inf(r);
     return;
   }
   fp h, i, j, rr, v, y3, z3;
@@ -702,9 +704,7 @@ __device__ inline void g1j_add_aff(g1j &r, const g1j &p, const g1a &q) {
       g1j_dbl(r, p);
       return;
     }
-    fp_zero(r.x);
-    fp_zero(r.y);
-    fp_zero(r.z);
+    g1j_set_inf(r);
     return;
   }
   fp h, hh, i, j, rr, v, x3, y3, z3;
@@ -739,9 +739,7 @@ __device__ inline void g1j_add_aff(g1j &r, const g1j &p, const g1a &q) {
 __device__ inline void g1j_mul_be_j(g1j &r, const g1j &base,
                                     const uint8_t *be, int nbytes) {
   g1j acc;
-  fp_zero(acc.x);
-  fp_zero(acc.y);
-  fp_zero(acc.z);
+  g1j_set_inf(acc);
   for (int i = 0; i < nbytes; i++) {
     uint8_t byte = be[i];
     for (int b = 7; b >= 0; b--) {
@@ -755,9 +753,7 @@ __device__ inline void g1j_mul_be_j(g1j &r, const g1j &base,
 __device__ inline void g1j_mul_be(g1j &r, const g1a &p, const uint8_t *be,
                                   int nbytes) {
   g1j acc, base;
-  fp_zero(acc.x);
-  fp_zero(acc.y);
-  fp_zero(acc.z);
+  g1j_set_inf(acc);
   g1j_from_aff(base, p);
   for (int i = 0; i < nbytes; i++) {
     uint8_t byte = be[i];
@@ -769,32 +765,21 @@ __device__ inline void g1j_mul_be(g1j &r, const g1a &p, const uint8_t *be,
   r = acc;
 }
 
-__device__ inline bool g1_on_curve(const g1a &p) {
-  if (p.inf) return true;
-  fp l, rhs, b1;
-  fp_sqr(l, p.y);
-  fp_sqr(rhs, p.x);
-  fp_mul(rhs, rhs, p.x);
-  // b = 4
-  fp one;
-  fp_one(one);
-  fp_add(b1, one, one);
-  fp_add(b1, b1, b1);
-  fp_add(rhs, rhs, b1);
-  return fp_eq(l, rhs);
-}
-
 // ------------------------------------------------------------- G2 points ---
 
 __device__ __forceinline__ bool g2j_is_inf(const g2j &p) {
   return fp2_is_zero(p.z);
 }
 
+__device__ __forceinline__ void g2j_set_inf(g2j &p) {
+  fp2_zero(p.x);
+  fp2_zero(p.y);
+  fp2_zero(p.z);
+}
+
 __device__ inline void g2j_from_aff(g2j &r, const g2a &a) {
   if (a.inf) {
-    fp2_zero(r.x);
-    fp2_zero(r.y);
-    fp2_zero(r.z);
+    g2j_set_inf(r);
     return;
   }
   r.x = a.x;
@@ -871,9 +856,7 @@ __device__ inline void g2j_add(g2j &r, const g2j &p, const g2j &q) {
       g2j_dbl(r, p);
       return;
     }
-    fp2_zero(r.x);
-    fp2_zero(r.y);
-    fp2_zero(r.z);
+    g2j_set_inf(r);
     return;
   }
   fp2 h, i, j, rr, v, y3, z3, s1j;
@@ -923,9 +906,7 @@ __device__ inline void g2j_add_aff(g2j &r, const g2j &p, const g2a &q) {
       g2j_dbl(r, p);
       return;
     }
-    fp2_zero(r.x);
-    fp2_zero(r.y);
-    fp2_zero(r.z);
+    g2j_set_inf(r);
     return;
   }
   fp2 h, hh, i, j, rr, v, x3, y3, z3;
@@ -962,9 +943,7 @@ __device__ inline void g2j_mul2_u64(g2j &r1, g2j &r2, const g2a &p,
                                     uint64_t k1, uint64_t k2) {
   g2j base, a1, a2;
   g2j_from_aff(base, p);
-  fp2_zero(a1.x);
-  fp2_zero(a1.y);
-  fp2_zero(a1.z);
+  g2j_set_inf(a1);
   a2 = a1;
   for (int b = 0; b < 64; b++) {
     if ((k1 >> b) & 1) g2j_add(a1, a1, base);
@@ -978,9 +957,7 @@ __device__ inline void g2j_mul2_u64(g2j &r1, g2j &r2, const g2a &p,
 __device__ inline void g2j_mul_be(g2j &r, const g2a &p, const uint8_t *be,
                                   int nbytes) {
   g2j acc, base;
-  fp2_zero(acc.x);
-  fp2_zero(acc.y);
-  fp2_zero(acc.z);
+  g2j_set_inf(acc);
   g2j_from_aff(base, p);
   for (int i = 0; i < nbytes; i++) {
     uint8_t byte = be[i];
@@ -1010,17 +987,6 @@ __device__ inline void g2_b2(fp2 &b2) {
   fp2_mul_xi(b2, f);
 }
 
-__device__ inline bool g2_on_curve(const g2a &p) {
-  if (p.inf) return true;
-  fp2 l, rhs, b2;
-  fp2_sqr(l, p.y);
-  fp2_sqr(rhs, p.x);
-  fp2_mul(rhs, rhs, p.x);
-  g2_b2(b2);
-  fp2_add(rhs, rhs, b2);
-  return fp2_eq(l, rhs);
-}
-
 // psi endomorphism (constants validated by the generator)
 __device__ inline void psi_g2(g2a &r, const g2a &p) {
   if (p.inf) {
@@ -1037,15 +1003,12 @@ __device__ inline void psi_g2(g2a &r, const g2a &p) {
   r.inf = 0;
 }
 
-// fast G2 subgroup check: psi(Q) == -[|x|]Q (validated vs [r]Q in Python)
-__device__ inline bool g2_in_subgroup(const g2a &p) {
-  if (p.inf) return true;
-  g2a ps;
-  psi_g2(ps, p);
-  g2j xq;
-  g2j_mul_u64(xq, p, BLS_X_ABS);
-  // compare psi(Q) (affine) with -xq (jacobian): cross-multiply
+// the subgroup check's compare: psi(Q) == -xq for an affine, finite Q and
+// xq = [|x|]Q Jacobian (x < 0), cross-multiplied so nothing is inverted
+__device__ inline bool psi_eq_neg(const g2a &q, const g2j &xq) {
   if (g2j_is_inf(xq)) return false;
+  g2a ps;
+  psi_g2(ps, q);
   fp2 z2, z3, lx, ly, ny;
   fp2_sqr(z2, xq.z);
   fp2_mul(z3, z2, xq.z);
@@ -1053,6 +1016,28 @@ __device__ inline bool g2_in_subgroup(const g2a &p) {
   fp2_neg(ny, xq.y);
   fp2_mul(ly, ps.y, z3);
   return fp2_eq(lx, xq.x) && fp2_eq(ly, ny);
+}
+
+// fast G2 subgroup check: psi(Q) == -[|x|]Q (validated vs [r]Q in Python)
+__device__ inline bool g2_in_subgroup(const g2a &p) {
+  if (p.inf) return true;
+  g2j xq;
+  g2j_mul_u64(xq, p, BLS_X_ABS);
+  return psi_eq_neg(p, xq);
+}
+
+// G1 subgroup check: [r]P == O, r as 32 big-endian bytes
+__device__ inline bool g1_in_subgroup(const g1a &p) {
+  uint8_t be[32];
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    uint64_t limb = BLS_ORDER[3 - i];
+#pragma unroll
+    for (int j = 0; j < 8; j++) be[8 * i + j] = (uint8_t)(limb >> (56 - 8 * j));
+  }
+  g1j t;
+  g1j_mul_be(t, p, be, 32);
+  return g1j_is_inf(t);
 }
 
 // ---------------------------------------------------------- serialization ---
@@ -1102,21 +1087,6 @@ __device__ inline int g1_from_uncomp_trusted(g1a &r, const uint8_t *in) {
   if (!fp_from_be48(r.y, in + 48)) return -1;
   r.inf = 0;
   return 0;
-}
-
-__device__ inline int g1_from_uncomp(g1a &r, const uint8_t *in) {
-  if (in[0] & 0x40) {
-    for (int i = 0; i < 96; i++)
-      if (in[i] != (i == 0 ? 0x40 : 0)) return -1;
-    r.inf = 1;
-    fp_zero(r.x);
-    fp_zero(r.y);
-    return 0;
-  }
-  if (!fp_from_be48(r.x, in)) return -1;
-  if (!fp_from_be48(r.y, in + 48)) return -1;
-  r.inf = 0;
-  return g1_on_curve(r) ? 0 : -1;
 }
 
 __device__ inline void g1_to_uncomp(const g1a &p, uint8_t *out) {
@@ -2193,57 +2163,6 @@ __device__ inline void sswu_g2_dual(g2a out[2], const fp2 u[2]) {
   }
 }
 
-__device__ inline void iso_map_g2(g2a &out, const g2a &in) {
-  fp2 k[4], xn, xd, yn, yd, t;
-  // x_num
-  FP2_LOAD_C(k[0], ISO_XNUM0);
-  FP2_LOAD_C(k[1], ISO_XNUM1);
-  FP2_LOAD_C(k[2], ISO_XNUM2);
-  FP2_LOAD_C(k[3], ISO_XNUM3);
-  xn = k[3];
-  for (int i = 2; i >= 0; i--) {
-    fp2_mul(xn, xn, in.x);
-    fp2_add(xn, xn, k[i]);
-  }
-  FP2_LOAD_C(k[0], ISO_XDEN0);
-  FP2_LOAD_C(k[1], ISO_XDEN1);
-  FP2_LOAD_C(k[2], ISO_XDEN2);
-  xd = k[2];
-  for (int i = 1; i >= 0; i--) {
-    fp2_mul(xd, xd, in.x);
-    fp2_add(xd, xd, k[i]);
-  }
-  FP2_LOAD_C(k[0], ISO_YNUM0);
-  FP2_LOAD_C(k[1], ISO_YNUM1);
-  FP2_LOAD_C(k[2], ISO_YNUM2);
-  FP2_LOAD_C(k[3], ISO_YNUM3);
-  yn = k[3];
-  for (int i = 2; i >= 0; i--) {
-    fp2_mul(yn, yn, in.x);
-    fp2_add(yn, yn, k[i]);
-  }
-  FP2_LOAD_C(k[0], ISO_YDEN0);
-  FP2_LOAD_C(k[1], ISO_YDEN1);
-  FP2_LOAD_C(k[2], ISO_YDEN2);
-  FP2_LOAD_C(k[3], ISO_YDEN3);
-  yd = k[3];
-  for (int i = 2; i >= 0; i--) {
-    fp2_mul(yd, yd, in.x);
-    fp2_add(yd, yd, k[i]);
-  }
-  // single shared inversion: 1/(xd*yd), then multiply back
-  fp2 prod;
-  fp2_mul(prod, xd, yd);
-  fp2_inv(t, prod);
-  fp2 xdi, ydi;
-  fp2_mul(ydi, t, xd); // 1/yd
-  fp2_mul(xdi, t, yd); // 1/xd
-  fp2_mul(out.x, xn, xdi);
-  fp2_mul(out.y, yn, ydi);
-  fp2_mul(out.y, out.y, in.y);
-  out.inf = 0;
-}
-
 // iso_map emitting JACOBIAN coordinates — no inversion at all:
 // x = xn/xd, y = in.y*yn/yd maps to Z = xd*yd, X = xn*xd*yd^2,
 // Y = in.y*yn*yd^2*xd^3 (X/Z^2 = xn/xd, Y/Z^3 = in.y*yn/yd).
@@ -2319,9 +2238,7 @@ __device__ inline void psi_g2j(g2j &r, const g2j &p) {
 // [k]P with a Jacobian base (the few additions use the full add)
 __device__ inline void g2j_mul_u64_j(g2j &r, const g2j &base, uint64_t k) {
   g2j acc;
-  fp2_zero(acc.x);
-  fp2_zero(acc.y);
-  fp2_zero(acc.z);
+  g2j_set_inf(acc);
   for (int b = 63; b >= 0; b--) {
     g2j_dbl(acc, acc);
     if ((k >> b) & 1) g2j_add(acc, acc, base);
@@ -2389,6 +2306,66 @@ __device__ inline void g1_gen(g1a &g) {
   FP_LOAD_C(g.x, BLS_G1X);
   FP_LOAD_C(g.y, BLS_G1Y);
   g.inf = 0;
+}
+
+// ------------------------------------------------------- block reductions ---
+
+// LDS halving tree: folds lds[0..W) into lds[0] with op(r, a, b), r distinct
+// from a and b. Thread t has just stored lds[t]; the leading barrier
+// publishes those stores and each level ends with one, so lds[0] is visible
+// to every thread on return. A caller that reuses lds afterwards (a
+// grid-stride loop) still needs its own barrier after reading lds[0].
+template <typename T, int W, typename Op>
+__device__ __forceinline__ void block_tree_reduce(T *lds, int t, Op op) {
+  __syncthreads();
+  for (int s = W / 2; s > 0; s >>= 1) {
+    if (t < s) {
+      T r;
+      op(r, lds[t], lds[t + s]);
+      lds[t] = r;
+    }
+    __syncthreads();
+  }
+}
+
+// the two point sums as combine functors
+struct g1j_add_op {
+  __device__ __forceinline__ void operator()(g1j &r, const g1j &a,
+                                             const g1j &b) const {
+    g1j_add(r, a, b);
+  }
+};
+struct g2j_add_op {
+  __device__ __forceinline__ void operator()(g2j &r, const g2j &a,
+                                             const g2j &b) const {
+    g2j_add(r, a, b);
+  }
+};
+
+// One stage of a two-stage reduction: the block folds its contiguous span of
+// in[0..n) (thread-strided local fold, then the LDS tree) into
+// out[blockIdx.x]; a second one-block launch folds the partials. A thread
+// starts from its first element (no fold with the identity); only a thread
+// with no element takes ident(local). op(r, a, b) may be called with r == a.
+template <typename T, int W, typename Op, typename Ident>
+__device__ __forceinline__ void block_span_reduce(const T *__restrict__ in,
+                                                  uint64_t n,
+                                                  T *__restrict__ out, T *lds,
+                                                  Op op, Ident ident) {
+  uint64_t per = (n + gridDim.x - 1) / gridDim.x;
+  uint64_t lo = (uint64_t)blockIdx.x * per;
+  uint64_t hi = lo + per < n ? lo + per : n;
+  T local;
+  uint64_t i = lo + threadIdx.x;
+  if (i < hi) {
+    local = in[i];
+    for (i += W; i < hi; i += W) op(local, local, in[i]);
+  } else {
+    ident(local);
+  }
+  lds[threadIdx.x] = local;
+  block_tree_reduce<T, W>(lds, (int)threadIdx.x, op);
+  if (threadIdx.x == 0) out[blockIdx.x] = lds[0];
 }
 
 } // namespace m3xb

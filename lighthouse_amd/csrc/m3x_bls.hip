@@ -23,7 +23,14 @@ static bool dbg_sync() {
   }
   return v == 1;
 }
-#define DBG_STEP(ctx, name)                                                      do {                                                                             if (dbg_sync()) {                                                                hipError_t _e = hipStreamSynchronize((ctx)->stream);                           fprintf(stderr, "[m3x dbg] %s: %s\n", name, hipGetErrorString(_e));            fflush(stderr);                                                              }                                                                            } while (0)
+#define DBG_STEP(ctx, name)                                                    \
+  do {                                                                         \
+    if (dbg_sync()) {                                                          \
+      hipError_t _e = hipStreamSynchronize((ctx)->stream);                     \
+      fprintf(stderr, "[m3x dbg] %s: %s\n", name, hipGetErrorString(_e));      \
+      fflush(stderr);                                                          \
+    }                                                                          \
+  } while (0)
 
 using namespace m3xb;
 
@@ -49,15 +56,6 @@ struct BlsWork {
   int *verdict;    // [1]
 };
 
-__device__ void order_be_bytes(uint8_t be[32]) {
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    uint64_t limb = BLS_ORDER[3 - i];
-#pragma unroll
-    for (int j = 0; j < 8; j++) be[8 * i + j] = (uint8_t)(limb >> (56 - 8 * j));
-  }
-}
-
 // ---------------------------------------------------------------- kernels
 
 __global__ __launch_bounds__(64, 1) void k_bls_pk_decompress(const uint8_t *__restrict__ comp,
@@ -74,12 +72,8 @@ __global__ __launch_bounds__(64, 1) void k_bls_pk_decompress(const uint8_t *__re
     status[i] = -2;
     return;
   }
-  uint8_t be[32];
-  order_be_bytes(be);
-  g1j t;
-  g1j_mul_be(t, p, be, 32);
-  if (!g1j_is_inf(t)) {
-    status[i] = -4; // subgroup check failed
+  if (!g1_in_subgroup(p)) {
+    status[i] = -4;
     return;
   }
   g1_to_uncomp(p, uncomp + 96 * i);
@@ -114,9 +108,7 @@ __global__ __launch_bounds__(64, 1) void k_bls_aggregate_w(
   uint32_t k0 = offs[set], k1 = offs[set + 1];
   int lane = threadIdx.x;
   g1j acc;
-  fp_zero(acc.x);
-  fp_zero(acc.y);
-  fp_zero(acc.z);
+  g1j_set_inf(acc);
   bool bad = false;
   for (uint32_t k = k0 + lane; k < k1; k += 64) {
     g1a pk;
@@ -128,15 +120,7 @@ __global__ __launch_bounds__(64, 1) void k_bls_aggregate_w(
   }
   if (bad) atomicOr(w.fail, 1);
   lds[lane] = acc;
-  __syncthreads();
-  for (int sft = 32; sft > 0; sft >>= 1) {
-    if (lane < sft) {
-      g1j t;
-      g1j_add(t, lds[lane], lds[lane + sft]);
-      lds[lane] = t;
-    }
-    __syncthreads();
-  }
+  block_tree_reduce<g1j, 64>(lds, lane, g1j_add_op{});
   if (lane == 0) w.apk[set] = lds[0];
   __syncthreads(); // next grid-stride iteration reuses lds
   }
@@ -187,60 +171,15 @@ __global__ __launch_bounds__(64, 1) void k_bls_prepare(const uint8_t *__restrict
   w.p_scaled[i] = rp;
   if (sig.inf) {
     // infinity is a valid subgroup element; contributes nothing
-    fp2_zero(w.rsig[i].x);
-    fp2_zero(w.rsig[i].y);
-    fp2_zero(w.rsig[i].z);
+    g2j_set_inf(w.rsig[i]);
   } else {
     // [r]sigma and the psi subgroup check's [|x|]sigma share sigma's
     // doubling chain (blst.rs:73-77 deferred subgroup check)
     g2j rsig_j, xsig_j;
     g2j_mul2_u64(rsig_j, xsig_j, sig, rands[i], BLS_X_ABS);
     w.rsig[i] = rsig_j;
-    // psi(sigma) must equal -[|x|]sigma (x < 0): cross-multiplied compare
-    g2a ps;
-    psi_g2(ps, sig);
-    bool ok;
-    if (g2j_is_inf(xsig_j)) {
-      ok = false;
-    } else {
-      fp2 z2, z3, lx, ly, ny;
-      fp2_sqr(z2, xsig_j.z);
-      fp2_mul(z3, z2, xsig_j.z);
-      fp2_mul(lx, ps.x, z2);
-      fp2_neg(ny, xsig_j.y);
-      fp2_mul(ly, ps.y, z3);
-      ok = fp2_eq(lx, xsig_j.x) && fp2_eq(ly, ny);
-    }
-    if (!ok) {
-      atomicOr(w.fail, 1);
-      return;
-    }
+    if (!psi_eq_neg(sig, xsig_j)) atomicOr(w.fail, 1);
   }
-}
-
-
-// ---- WAVE-SPLIT prepare (round 2; was one ~30ms/lane serial kernel) ----
-// pass 1: decompress sigma (n lanes; the sqrt pow chain dominates)
-__global__ __launch_bounds__(64, 1) void k_bls_sigdec(
-    const uint8_t *__restrict__ sigs, uint64_t n, BlsWork w) {
-  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  g2a sig;
-  if (g2_decompress(sig, sigs + 96 * i) != 0) {
-    atomicOr(w.fail, 1);
-    sig.inf = 1; // harmless placeholder; verdict is already forced false
-  }
-  g2j out;
-  if (sig.inf) {
-    fp2_zero(out.x);
-    fp2_zero(out.y);
-    fp2_zero(out.z);
-  } else {
-    out.x = sig.x;
-    out.y = sig.y;
-    fp2_one(out.z);
-  }
-  w.sig_aff[i] = out;
 }
 
 // [k]B for an affine G2 base with MIXED adds (24 vs 43 fp-muls per add);
@@ -248,9 +187,7 @@ __global__ __launch_bounds__(64, 1) void k_bls_sigdec(
 // cost LESS total than the round-1 shared-doubling chain of FULL adds.
 __device__ inline void g2_mul_u64_aff(g2j &r, const g2a &base, uint64_t k) {
   g2j acc;
-  fp2_zero(acc.x);
-  fp2_zero(acc.y);
-  fp2_zero(acc.z);
+  g2j_set_inf(acc);
   for (int b = 63; b >= 0; b--) {
     g2j_dbl(acc, acc);
     if ((k >> b) & 1) g2j_add_aff(acc, acc, base);
@@ -261,102 +198,12 @@ __device__ inline void g2_mul_u64_aff(g2j &r, const g2a &base, uint64_t k) {
 // [k]B for an affine G1 base with mixed adds
 __device__ inline void g1_mul_u64_aff(g1j &r, const g1a &base, uint64_t k) {
   g1j acc;
-  fp_zero(acc.x);
-  fp_zero(acc.y);
-  fp_zero(acc.z);
+  g1j_set_inf(acc);
   for (int b = 63; b >= 0; b--) {
     g1j_dbl(acc, acc);
     if ((k >> b) & 1) g1j_add_aff(acc, acc, base);
   }
   r = acc;
-}
-
-// pass 2: the scalar-mult work, TWO wave-uniform classes over 2n lanes
-// (2 waves/SIMD at the C2 shape):
-//   class A (lane i):   rsig[i] = [r_i] sigma_i
-//   class B (lane n+i): p_scaled[i] = [r_i] apk_i  AND the deferred
-//                       psi-subgroup check psi(sigma) == -[|x|]sigma
-//                       (blst.rs:73-77)
-__global__ __launch_bounds__(64, 1) void k_bls_prep_mults(
-    const uint8_t *__restrict__ pks, const uint32_t *__restrict__ offs,
-    const uint64_t *__restrict__ rands, uint64_t n, BlsWork w) {
-  uint64_t lane = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (lane >= 2 * n) return;
-  if (lane < n) {
-    uint64_t i = lane;
-    g2j sj = w.sig_aff[i];
-    if (g2j_is_inf(sj)) {
-      // infinity contributes nothing to the signature sum
-      fp2_zero(w.rsig[i].x);
-      fp2_zero(w.rsig[i].y);
-      fp2_zero(w.rsig[i].z);
-      return;
-    }
-    g2a sig;
-    sig.x = sj.x;
-    sig.y = sj.y;
-    sig.inf = 0;
-    g2j rs;
-    g2_mul_u64_aff(rs, sig, rands[i]);
-    w.rsig[i] = rs;
-    return;
-  }
-  uint64_t i = lane - n;
-  uint32_t k0 = offs[i], k1 = offs[i + 1];
-  if (k1 <= k0) {
-    atomicOr(w.fail, 1);
-    return;
-  }
-  g1j rp;
-  if (k1 - k0 == 1) {
-    g1a pk;
-    if (g1_from_uncomp_trusted(pk, pks + 96 * (uint64_t)k0) != 0) {
-      atomicOr(w.fail, 1);
-      return;
-    }
-    if (pk.inf) { // aggregate at infinity -> invalid
-      atomicOr(w.fail, 1);
-      return;
-    }
-    g1_mul_u64_aff(rp, pk, rands[i]); // mixed adds on the affine base
-  } else {
-    g1j apk = w.apk[i]; // precomputed by k_bls_aggregate_w
-    if (g1j_is_inf(apk)) {
-      atomicOr(w.fail, 1);
-      return;
-    }
-    uint8_t rbe[8];
-#pragma unroll
-    for (int b = 0; b < 8; b++)
-      rbe[b] = (uint8_t)(rands[i] >> (56 - 8 * b));
-    g1j_mul_be_j(rp, apk, rbe, 8);
-  }
-  w.p_scaled[i] = rp;
-  // deferred subgroup check (skipped for infinity: valid element)
-  g2j sj = w.sig_aff[i];
-  if (!g2j_is_inf(sj)) {
-    g2a sig;
-    sig.x = sj.x;
-    sig.y = sj.y;
-    sig.inf = 0;
-    g2j xsig_j;
-    g2_mul_u64_aff(xsig_j, sig, BLS_X_ABS);
-    g2a ps;
-    psi_g2(ps, sig);
-    bool ok;
-    if (g2j_is_inf(xsig_j)) {
-      ok = false;
-    } else {
-      fp2 z2, z3, lx, ly, ny;
-      fp2_sqr(z2, xsig_j.z);
-      fp2_mul(z3, z2, xsig_j.z);
-      fp2_mul(lx, ps.x, z2);
-      fp2_neg(ny, xsig_j.y);
-      fp2_mul(ly, ps.y, z3);
-      ok = fp2_eq(lx, xsig_j.x) && fp2_eq(ly, ny);
-    }
-    if (!ok) atomicOr(w.fail, 1);
-  }
 }
 
 __global__ __launch_bounds__(64, 1) void k_bls_h2c(const uint8_t *__restrict__ msgs, uint64_t n,
@@ -376,8 +223,7 @@ __global__ __launch_bounds__(64, 1) void k_bls_h2c_expand(
   expand_message_xmd32(msgs + 32 * i, w.uni + 256 * i);
 }
 
-__global__ __launch_bounds__(64, 2) void k_bls_h2c_map(uint64_t n,
-                                                       BlsWork w) {
+__device__ __forceinline__ void h2c_map_lane(uint64_t n, const BlsWork &w) {
   uint64_t lane = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (lane >= 2 * n) return;
   int role = lane < n ? 0 : 1; // which of the two RO points
@@ -396,6 +242,22 @@ __global__ __launch_bounds__(64, 2) void k_bls_h2c_map(uint64_t n,
   // clearing the sum — the fin pass is then one mixed add per set
   clear_cofactor_g2j(cleared, pt);
   w.h2c_pts[lane] = cleared;
+}
+
+// default register budget: the high-occupancy regime (n > latency_max)
+__global__ __launch_bounds__(64, 2) void k_bls_h2c_map(uint64_t n,
+                                                       BlsWork w) {
+  h2c_map_lane(n, w);
+}
+
+// LATENCY-REGIME register-budget twin (as k_bls_sigdec_lat and
+// k_bls_prep_mults3 are): at n <= latency_max these kernels run 1-2
+// waves/SIMD, so granting each wave the idle register file (512 or 256
+// VGPRs vs the ~130 the default allocation picks) trades nothing and
+// removes scratch spill round-trips from the serial chains.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void k_bls_h2c_map_lat(uint64_t n, BlsWork w) {
+  h2c_map_lane(n, w);
 }
 
 __global__ __launch_bounds__(64, 1) void k_bls_h2c_fin(uint64_t n,
@@ -486,28 +348,10 @@ constexpr uint32_t kReduceMaxBlocks = 256;
 __global__ __launch_bounds__(kReduceThreads) void k_bls_reduce_gt(
     const fp12m *__restrict__ in, uint64_t n, fp12m *__restrict__ out) {
   __shared__ fp12m lds[kReduceThreads];
-  uint64_t per = (n + gridDim.x - 1) / gridDim.x;
-  uint64_t lo = (uint64_t)blockIdx.x * per;
-  uint64_t hi = lo + per < n ? lo + per : n;
-  fp12m local;
-  uint64_t i = lo + threadIdx.x;
-  if (i < hi) {
-    f12_copy(local, in[i]);
-    for (i += kReduceThreads; i < hi; i += kReduceThreads)
-      f12_mul_nn(local, local, in[i]);
-  } else {
-    f12_one(local);
-  }
-  lds[threadIdx.x] = local;
-  __syncthreads();
-  for (int s = kReduceThreads / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      f12_mul_nn(local, lds[threadIdx.x], lds[threadIdx.x + s]);
-      f12_copy(lds[threadIdx.x], local);
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[blockIdx.x] = lds[0];
+  block_span_reduce<fp12m, kReduceThreads>(
+      in, n, out, lds,
+      [](fp12m &r, const fp12m &a, const fp12m &b) { f12_mul_nn(r, a, b); },
+      [](fp12m &r) { f12_one(r); });
 }
 
 // two-stage sum of r_i*sigma_i, same shape (a thread with no element
@@ -515,31 +359,8 @@ __global__ __launch_bounds__(kReduceThreads) void k_bls_reduce_gt(
 __global__ __launch_bounds__(kReduceThreads) void k_bls_reduce_sig(
     const g2j *__restrict__ in, uint64_t n, g2j *__restrict__ out) {
   __shared__ g2j lds[kReduceThreads];
-  uint64_t per = (n + gridDim.x - 1) / gridDim.x;
-  uint64_t lo = (uint64_t)blockIdx.x * per;
-  uint64_t hi = lo + per < n ? lo + per : n;
-  g2j local;
-  uint64_t i = lo + threadIdx.x;
-  if (i < hi) {
-    local = in[i];
-    for (i += kReduceThreads; i < hi; i += kReduceThreads)
-      g2j_add(local, local, in[i]);
-  } else {
-    fp2_zero(local.x);
-    fp2_zero(local.y);
-    fp2_zero(local.z);
-  }
-  lds[threadIdx.x] = local;
-  __syncthreads();
-  for (int s = kReduceThreads / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      g2j t;
-      g2j_add(t, lds[threadIdx.x], lds[threadIdx.x + s]);
-      lds[threadIdx.x] = t;
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[blockIdx.x] = lds[0];
+  block_span_reduce<g2j, kReduceThreads>(in, n, out, lds, g2j_add_op{},
+                                         [](g2j &r) { g2j_set_inf(r); });
 }
 
 // signature pair: sig_gt = miller(-g1, sig_sum), one cooperative wave.
@@ -596,9 +417,7 @@ __global__ __launch_bounds__(64, 1) void k_bls_sig_aggregate_w(
   __shared__ g2j lds[64];
   int lane = threadIdx.x;
   g2j acc;
-  fp2_zero(acc.x);
-  fp2_zero(acc.y);
-  fp2_zero(acc.z);
+  g2j_set_inf(acc);
   bool bad = false;
   for (uint64_t i = lane; i < n; i += 64) {
     g2a sg;
@@ -614,15 +433,7 @@ __global__ __launch_bounds__(64, 1) void k_bls_sig_aggregate_w(
   }
   if (bad) atomicOr(fail, 1);
   lds[lane] = acc;
-  __syncthreads();
-  for (int sft = 32; sft > 0; sft >>= 1) {
-    if (lane < sft) {
-      g2j t;
-      g2j_add(t, lds[lane], lds[lane + sft]);
-      lds[lane] = t;
-    }
-    __syncthreads();
-  }
+  block_tree_reduce<g2j, 64>(lds, lane, g2j_add_op{});
   if (lane == 0 && !*fail) {
     g2a a;
     g2j_to_aff(a, lds[0]);
@@ -668,12 +479,18 @@ __global__ void k_bls_expand_dst(const uint8_t *__restrict__ msg,
   expand_message_xmd_gen(msg, msg_len, dst, dst_len, len_in_bytes, out);
 }
 
+// a stored sig_aff entry (z = 1: affine x, y; z = 0: infinity) as a g2a
+__device__ __forceinline__ void sig_aff_load(g2a &sig, const g2j &sj) {
+  sig.x = sj.x;
+  sig.y = sj.y;
+  sig.inf = g2j_is_inf(sj) ? 1 : 0;
+}
 
-// LATENCY-REGIME register-budget twins: at n <= 2^18 these kernels run
-// 1-2 waves/SIMD, so granting each wave the idle register file (512 or
-// 256 VGPRs vs the ~130 the default allocation picks) trades nothing
-// and removes scratch spill round-trips from the serial chains. The
-// default-budget forms stay for the high-occupancy regime.
+// ---- WAVE-SPLIT prepare, latency regime (n <= latency_max): the fused
+// k_bls_prepare was one ~30 ms/lane serial kernel. Pass 1 decompresses
+// sigma (n lanes; the sqrt pow chain dominates), pass 2 is the scalar-mult
+// work in wave-uniform classes. Both take the full register budget (see
+// k_bls_h2c_map_lat).
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void k_bls_sigdec_lat(const uint8_t *__restrict__ sigs, uint64_t n,
                       BlsWork w) {
@@ -682,108 +499,17 @@ void k_bls_sigdec_lat(const uint8_t *__restrict__ sigs, uint64_t n,
   g2a sig;
   if (g2_decompress(sig, sigs + 96 * i) != 0) {
     atomicOr(w.fail, 1);
-    sig.inf = 1;
+    sig.inf = 1; // harmless placeholder; the verdict is already forced false
   }
   g2j out;
-  if (sig.inf) {
-    fp2_zero(out.x);
-    fp2_zero(out.y);
-    fp2_zero(out.z);
-  } else {
-    out.x = sig.x;
-    out.y = sig.y;
-    fp2_one(out.z);
-  }
+  g2j_from_aff(out, sig);
   w.sig_aff[i] = out;
 }
 
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void k_bls_prep_mults_lat(const uint8_t *__restrict__ pks,
-                          const uint32_t *__restrict__ offs,
-                          const uint64_t *__restrict__ rands, uint64_t n,
-                          BlsWork w) {
-  uint64_t lane = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (lane >= 2 * n) return;
-  if (lane < n) {
-    uint64_t i = lane;
-    g2j sj = w.sig_aff[i];
-    if (g2j_is_inf(sj)) {
-      fp2_zero(w.rsig[i].x);
-      fp2_zero(w.rsig[i].y);
-      fp2_zero(w.rsig[i].z);
-      return;
-    }
-    g2a sig;
-    sig.x = sj.x;
-    sig.y = sj.y;
-    sig.inf = 0;
-    g2j rs;
-    g2_mul_u64_aff(rs, sig, rands[i]);
-    w.rsig[i] = rs;
-    return;
-  }
-  uint64_t i = lane - n;
-  uint32_t k0 = offs[i], k1 = offs[i + 1];
-  if (k1 <= k0) {
-    atomicOr(w.fail, 1);
-    return;
-  }
-  g1j rp;
-  if (k1 - k0 == 1) {
-    g1a pk;
-    if (g1_from_uncomp_trusted(pk, pks + 96 * (uint64_t)k0) != 0) {
-      atomicOr(w.fail, 1);
-      return;
-    }
-    if (pk.inf) {
-      atomicOr(w.fail, 1);
-      return;
-    }
-    g1_mul_u64_aff(rp, pk, rands[i]);
-  } else {
-    g1j apk = w.apk[i];
-    if (g1j_is_inf(apk)) {
-      atomicOr(w.fail, 1);
-      return;
-    }
-    uint8_t rbe[8];
-#pragma unroll
-    for (int b = 0; b < 8; b++)
-      rbe[b] = (uint8_t)(rands[i] >> (56 - 8 * b));
-    g1j_mul_be_j(rp, apk, rbe, 8);
-  }
-  w.p_scaled[i] = rp;
-  g2j sj = w.sig_aff[i];
-  if (!g2j_is_inf(sj)) {
-    g2a sig;
-    sig.x = sj.x;
-    sig.y = sj.y;
-    sig.inf = 0;
-    g2j xsig_j;
-    g2_mul_u64_aff(xsig_j, sig, BLS_X_ABS);
-    g2a ps;
-    psi_g2(ps, sig);
-    bool ok;
-    if (g2j_is_inf(xsig_j)) {
-      ok = false;
-    } else {
-      fp2 z2, z3, lx, ly, ny;
-      fp2_sqr(z2, xsig_j.z);
-      fp2_mul(z3, z2, xsig_j.z);
-      fp2_mul(lx, ps.x, z2);
-      fp2_neg(ny, xsig_j.y);
-      fp2_mul(ly, ps.y, z3);
-      ok = fp2_eq(lx, xsig_j.x) && fp2_eq(ly, ny);
-    }
-    if (!ok) atomicOr(w.fail, 1);
-  }
-}
-
 // THREE-class latency-regime mult pass (3n lanes): A [r]sigma,
-// B [|x|]sigma + psi subgroup check, C [r]apk on G1. Same total work as
-// the 2-class form but the critical lane shrinks from (G1 mult + x-mult)
-// to max(one chain) and wave count rises 3n/64 — pure latency win for
-// small/medium batches.
+// B [|x|]sigma + psi subgroup check, C [r]apk on G1. Every class is
+// wave-uniform, no lane carries more than one chain, and the wave count
+// is 3n/64 — a pure latency win for small and medium batches.
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_bls_prep_mults3(const uint8_t *__restrict__ pks,
                        const uint32_t *__restrict__ offs,
@@ -794,46 +520,24 @@ void k_bls_prep_mults3(const uint8_t *__restrict__ pks,
   int cls = lane < n ? 0 : (lane < 2 * n ? 1 : 2);
   uint64_t i = lane - (uint64_t)cls * n;
   if (cls == 0) { // A: rsig[i] = [r_i] sigma
-    g2j sj = w.sig_aff[i];
-    if (g2j_is_inf(sj)) {
-      fp2_zero(w.rsig[i].x);
-      fp2_zero(w.rsig[i].y);
-      fp2_zero(w.rsig[i].z);
+    g2a sig;
+    sig_aff_load(sig, w.sig_aff[i]);
+    if (sig.inf) { // infinity contributes nothing to the signature sum
+      g2j_set_inf(w.rsig[i]);
       return;
     }
-    g2a sig;
-    sig.x = sj.x;
-    sig.y = sj.y;
-    sig.inf = 0;
     g2j rs;
     g2_mul_u64_aff(rs, sig, rands[i]);
     w.rsig[i] = rs;
     return;
   }
-  if (cls == 1) { // B: deferred psi subgroup check
-    g2j sj = w.sig_aff[i];
-    if (g2j_is_inf(sj)) return; // infinity is a valid element
+  if (cls == 1) { // B: deferred psi subgroup check (blst.rs:73-77)
     g2a sig;
-    sig.x = sj.x;
-    sig.y = sj.y;
-    sig.inf = 0;
+    sig_aff_load(sig, w.sig_aff[i]);
+    if (sig.inf) return; // infinity is a valid element
     g2j xsig_j;
     g2_mul_u64_aff(xsig_j, sig, BLS_X_ABS);
-    g2a ps;
-    psi_g2(ps, sig);
-    bool ok;
-    if (g2j_is_inf(xsig_j)) {
-      ok = false;
-    } else {
-      fp2 z2, z3, lx, ly, ny;
-      fp2_sqr(z2, xsig_j.z);
-      fp2_mul(z3, z2, xsig_j.z);
-      fp2_mul(lx, ps.x, z2);
-      fp2_neg(ny, xsig_j.y);
-      fp2_mul(ly, ps.y, z3);
-      ok = fp2_eq(lx, xsig_j.x) && fp2_eq(ly, ny);
-    }
-    if (!ok) atomicOr(w.fail, 1);
+    if (!psi_eq_neg(sig, xsig_j)) atomicOr(w.fail, 1);
     return;
   }
   // C: p_scaled[i] = [r_i] apk
@@ -869,68 +573,31 @@ void k_bls_prep_mults3(const uint8_t *__restrict__ pks,
   w.p_scaled[i] = rp;
 }
 
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void k_bls_h2c_map_lat(uint64_t n, BlsWork w) {
-  uint64_t lane = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (lane >= 2 * n) return;
-  int role = lane < n ? 0 : 1;
-  uint64_t i = role == 0 ? lane : lane - n;
-  const uint8_t *uni = w.uni + 256 * i + 128 * role;
-  fp2 u;
-  h2f_from_be64(u.c0, uni);
-  h2f_from_be64(u.c1, uni + 64);
-  g2a q;
-  sswu_g2(q, u);
-  g2j pt, cleared;
-  iso_map_g2_j(pt, q);
-  clear_cofactor_g2j(cleared, pt);
-  w.h2c_pts[lane] = cleared;
-}
-
 int run_verify(m3x_ctx *ctx, const void *msgs_dev, const void *sigs_dev,
                const void *pks_dev, const void *offs_dev,
                const void *rands_dev, uint64_t n, int32_t *out) {
   BlsWork w;
-  uint64_t bytes = 0;
-  auto align = [](uint64_t x) { return (x + 255) & ~255ull; };
-  uint64_t off_apk = bytes; bytes += align(n * sizeof(g1j));
-  uint64_t off_aggidx = bytes; bytes += align(n * 8);
-  uint64_t off_aggcnt = bytes; bytes += 256;
-  uint64_t off_p = bytes; bytes += align(n * sizeof(g1j));
-  uint64_t off_h = bytes; bytes += align(n * sizeof(g2j));
-  uint64_t off_uni = bytes; bytes += align(n * 256);
-  uint64_t off_hpts = bytes; bytes += align(2 * n * sizeof(g2j));
-  uint64_t off_r = bytes; bytes += align(n * sizeof(g2j));
-  uint64_t off_sa = bytes; bytes += align(n * sizeof(g2j));
-  uint64_t off_f = bytes; bytes += align(2 * n * sizeof(fp12m)); // split miller: 2n partials
-  uint64_t off_fail = bytes; bytes += 256;
-  uint64_t off_sig_stage = bytes; bytes += align(kReduceMaxBlocks * sizeof(g2j));
-  uint64_t off_sum = bytes; bytes += align(sizeof(g2j));
-  uint64_t off_gt_stage = bytes; bytes += align(kReduceMaxBlocks * sizeof(fp12m));
-  uint64_t off_gt = bytes; bytes += align(sizeof(fp12m));
-  uint64_t off_sig_gt = bytes; bytes += align(sizeof(fp12m));
-  uint64_t off_v = bytes; bytes += 256;
-  int rc = m3x::ensure_scratch(ctx, &ctx->scratch_a, &ctx->scratch_a_bytes,
-                               bytes);
+  int rc = m3x::carve_scratch(
+      ctx, &ctx->scratch_a, &ctx->scratch_a_bytes, [&](m3x::ScratchCarver &c) {
+        w.apk = c.take<g1j>(n);
+        w.agg_idx = c.take<uint64_t>(n);
+        w.agg_count = c.take<uint32_t>(1);
+        w.p_scaled = c.take<g1j>(n);
+        w.h2c = c.take<g2j>(n);
+        w.uni = c.take<uint8_t>(n * 256);
+        w.h2c_pts = c.take<g2j>(2 * n);
+        w.rsig = c.take<g2j>(n);
+        w.sig_aff = c.take<g2j>(n);
+        w.fparts = c.take<fp12m>(2 * n); // split miller: 2n partials
+        w.fail = c.take<int>(1);
+        w.sig_stage = c.take<g2j>(kReduceMaxBlocks);
+        w.sig_sum = c.take<g2j>(1);
+        w.gt_stage = c.take<fp12m>(kReduceMaxBlocks);
+        w.gt_parts = c.take<fp12m>(1);
+        w.sig_gt = c.take<fp12m>(1);
+        w.verdict = c.take<int>(1);
+      });
   if (rc != M3X_OK) return rc;
-  uint8_t *base = ctx->scratch_a;
-  w.apk = reinterpret_cast<g1j *>(base + off_apk);
-  w.agg_idx = reinterpret_cast<uint64_t *>(base + off_aggidx);
-  w.agg_count = reinterpret_cast<uint32_t *>(base + off_aggcnt);
-  w.p_scaled = reinterpret_cast<g1j *>(base + off_p);
-  w.h2c = reinterpret_cast<g2j *>(base + off_h);
-  w.uni = base + off_uni;
-  w.h2c_pts = reinterpret_cast<g2j *>(base + off_hpts);
-  w.rsig = reinterpret_cast<g2j *>(base + off_r);
-  w.sig_aff = reinterpret_cast<g2j *>(base + off_sa);
-  w.fparts = reinterpret_cast<fp12m *>(base + off_f);
-  w.fail = reinterpret_cast<int *>(base + off_fail);
-  w.sig_stage = reinterpret_cast<g2j *>(base + off_sig_stage);
-  w.sig_sum = reinterpret_cast<g2j *>(base + off_sum);
-  w.gt_stage = reinterpret_cast<fp12m *>(base + off_gt_stage);
-  w.gt_parts = reinterpret_cast<fp12m *>(base + off_gt);
-  w.sig_gt = reinterpret_cast<fp12m *>(base + off_sig_gt);
-  w.verdict = reinterpret_cast<int *>(base + off_v);
   M3X_HIP_CHECK(hipMemsetAsync(w.fail, 0, 4, ctx->stream));
   M3X_HIP_CHECK(hipMemsetAsync(w.agg_count, 0, 4, ctx->stream));
   uint32_t blocks = (uint32_t)((n + 63) / 64);
@@ -944,8 +611,14 @@ int run_verify(m3x_ctx *ctx, const void *msgs_dev, const void *sigs_dev,
                        (const uint32_t *)offs_dev, w);
   }
   m3x::time_end(ctx, M3X_K_BLS_AGG);
+  // Above latency_max sets the kernels are issue-bound and the fused,
+  // default-register-budget forms win; at or below it the latency-regime
+  // forms do. Read per call (as M3X_SMALL_MILLER is) so a small test batch
+  // can be sent through the large-batch kernels.
+  uint64_t latency_max = 1ull << 18;
+  if (const char *e = getenv("M3X_LATENCY_MAX")) latency_max = strtoull(e, nullptr, 10);
   m3x::time_begin(ctx, M3X_K_BLS_PREPARE);
-  if (n > (1ull << 18)) {
+  if (n > latency_max) {
     // issue-bound regime: the fused shared-chain kernel does less work
     hipLaunchKernelGGL(k_bls_prepare, dim3(blocks), dim3(64), 0,
                        ctx->stream, (const uint8_t *)sigs_dev,
@@ -972,7 +645,7 @@ int run_verify(m3x_ctx *ctx, const void *msgs_dev, const void *sigs_dev,
     uint32_t blocks2 = (uint32_t)((2 * n + 63) / 64);
     hipLaunchKernelGGL(k_bls_h2c_expand, dim3(blocks), dim3(64), 0,
                        ctx->stream2, (const uint8_t *)msgs_dev, n, w);
-    if (n <= (1ull << 18))
+    if (n <= latency_max)
       hipLaunchKernelGGL(k_bls_h2c_map_lat, dim3(blocks2), dim3(64), 0,
                          ctx->stream2, n, w);
     else
@@ -1072,35 +745,17 @@ int32_t m3x_bls_pk_decompress(m3x_ctx *ctx, const uint8_t *comp, uint64_t n,
   if (!ctx || n == 0) return M3X_ERR_ARG;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   M3X_HIP_CHECK(hipSetDevice(ctx->device));
-  // single cleanup path: partial allocation failure frees prior buffers,
-  // and every copy is checked (a failed upload must not run the kernel on
-  // stale device memory and report "invalid")
-  uint8_t *comp_d = nullptr, *unc_d = nullptr;
-  int32_t *st_d = nullptr;
-  int32_t rc = M3X_ERR_HIP;
-  if (hipMalloc(&comp_d, n * 48) != hipSuccess) goto out;
-  if (hipMalloc(&unc_d, n * 96) != hipSuccess) goto out;
-  if (hipMalloc(&st_d, n * 4) != hipSuccess) goto out;
-  if (hipMemcpyAsync(comp_d, comp, n * 48, hipMemcpyHostToDevice,
-                     ctx->stream) != hipSuccess)
-    goto out;
-  {
-    uint32_t blocks = (uint32_t)((n + 63) / 64);
-    hipLaunchKernelGGL(k_bls_pk_decompress, dim3(blocks), dim3(64), 0,
-                       ctx->stream, comp_d, n, unc_d, st_d);
-  }
-  if (hipMemcpyAsync(uncomp, unc_d, n * 96, hipMemcpyDeviceToHost,
-                     ctx->stream) != hipSuccess)
-    goto out;
-  if (hipMemcpyAsync(status, st_d, n * 4, hipMemcpyDeviceToHost,
-                     ctx->stream) != hipSuccess)
-    goto out;
-  if (hipStreamSynchronize(ctx->stream) == hipSuccess) rc = M3X_OK;
-out:
-  if (comp_d) (void)hipFree(comp_d);
-  if (unc_d) (void)hipFree(unc_d);
-  if (st_d) (void)hipFree(st_d);
-  return rc;
+  m3x::DevTemps tmp(ctx->stream);
+  const uint8_t *comp_d = tmp.upload(comp, n * 48);
+  uint8_t *unc_d = tmp.alloc(n * 96);
+  int32_t *st_d = tmp.alloc<int32_t>(n * 4);
+  if (!tmp.ok()) return M3X_ERR_HIP;
+  uint32_t blocks = (uint32_t)((n + 63) / 64);
+  hipLaunchKernelGGL(k_bls_pk_decompress, dim3(blocks), dim3(64), 0,
+                     ctx->stream, comp_d, n, unc_d, st_d);
+  tmp.download(uncomp, unc_d, n * 96);
+  tmp.download(status, st_d, n * 4);
+  return tmp.sync() ? M3X_OK : M3X_ERR_HIP;
 }
 
 int32_t m3x_bls_expand_test(m3x_ctx *ctx, const uint8_t *msg,
@@ -1112,26 +767,15 @@ int32_t m3x_bls_expand_test(m3x_ctx *ctx, const uint8_t *msg,
     return M3X_ERR_ARG;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   M3X_HIP_CHECK(hipSetDevice(ctx->device));
-  uint8_t *buf_d = nullptr;
-  int32_t rc = M3X_ERR_HIP;
-  if (hipMalloc(&buf_d, 1024 + 256) != hipSuccess) return M3X_ERR_HIP;
-  if (msg_len &&
-      hipMemcpyAsync(buf_d, msg, msg_len, hipMemcpyHostToDevice,
-                     ctx->stream) != hipSuccess)
-    goto out;
-  if (hipMemcpyAsync(buf_d + 768, dst, dst_len, hipMemcpyHostToDevice,
-                     ctx->stream) != hipSuccess)
-    goto out;
+  m3x::DevTemps tmp(ctx->stream);
+  const uint8_t *msg_d = tmp.upload(msg, msg_len);
+  const uint8_t *dst_d = tmp.upload(dst, dst_len);
+  uint8_t *out_d = tmp.alloc(256);
+  if (!tmp.ok()) return M3X_ERR_HIP;
   hipLaunchKernelGGL(k_bls_expand_dst, dim3(1), dim3(1), 0, ctx->stream,
-                     buf_d, msg_len, buf_d + 768, dst_len, len_in_bytes,
-                     buf_d + 1024);
-  if (hipMemcpyAsync(out, buf_d + 1024, len_in_bytes, hipMemcpyDeviceToHost,
-                     ctx->stream) != hipSuccess)
-    goto out;
-  if (hipStreamSynchronize(ctx->stream) == hipSuccess) rc = M3X_OK;
-out:
-  (void)hipFree(buf_d);
-  return rc;
+                     msg_d, msg_len, dst_d, dst_len, len_in_bytes, out_d);
+  tmp.download(out, out_d, len_in_bytes);
+  return tmp.sync() ? M3X_OK : M3X_ERR_HIP;
 }
 
 int32_t m3x_bls_h2c_test(m3x_ctx *ctx, const uint8_t *msg, uint32_t msg_len,
@@ -1141,30 +785,16 @@ int32_t m3x_bls_h2c_test(m3x_ctx *ctx, const uint8_t *msg, uint32_t msg_len,
     return M3X_ERR_ARG;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   M3X_HIP_CHECK(hipSetDevice(ctx->device));
-  uint8_t *buf_d = nullptr;
-  int32_t rc = M3X_ERR_HIP;
-  if (hipMalloc(&buf_d, 1024 + 192 + 256) != hipSuccess) return M3X_ERR_HIP;
-  if (msg_len &&
-      hipMemcpyAsync(buf_d, msg, msg_len, hipMemcpyHostToDevice,
-                     ctx->stream) != hipSuccess)
-    goto out;
-  if (hipMemcpyAsync(buf_d + 768, dst, dst_len, hipMemcpyHostToDevice,
-                     ctx->stream) != hipSuccess)
-    goto out;
-  hipLaunchKernelGGL(k_bls_h2c_dst, dim3(1), dim3(1), 0, ctx->stream, buf_d,
-                     msg_len, buf_d + 768, dst_len, buf_d + 1024,
-                     buf_d + 1024 + 192);
-  if (hipMemcpyAsync(out_uncomp, buf_d + 1024, 192, hipMemcpyDeviceToHost,
-                     ctx->stream) != hipSuccess)
-    goto out;
-  if (out_uniform &&
-      hipMemcpyAsync(out_uniform, buf_d + 1024 + 192, 256,
-                     hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-    goto out;
-  if (hipStreamSynchronize(ctx->stream) == hipSuccess) rc = M3X_OK;
-out:
-  (void)hipFree(buf_d);
-  return rc;
+  m3x::DevTemps tmp(ctx->stream);
+  const uint8_t *msg_d = tmp.upload(msg, msg_len);
+  const uint8_t *dst_d = tmp.upload(dst, dst_len);
+  uint8_t *pt_d = tmp.alloc(192), *uni_d = tmp.alloc(256);
+  if (!tmp.ok()) return M3X_ERR_HIP;
+  hipLaunchKernelGGL(k_bls_h2c_dst, dim3(1), dim3(1), 0, ctx->stream, msg_d,
+                     msg_len, dst_d, dst_len, pt_d, uni_d);
+  tmp.download(out_uncomp, pt_d, 192);
+  if (out_uniform) tmp.download(out_uniform, uni_d, 256);
+  return tmp.sync() ? M3X_OK : M3X_ERR_HIP;
 }
 
 int32_t m3x_bls_sig_aggregate(m3x_ctx *ctx, const uint8_t *sigs, uint64_t n,
@@ -1172,24 +802,18 @@ int32_t m3x_bls_sig_aggregate(m3x_ctx *ctx, const uint8_t *sigs, uint64_t n,
   if (!ctx || n == 0) return M3X_ERR_ARG;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   M3X_HIP_CHECK(hipSetDevice(ctx->device));
-  uint8_t *sigs_d, *out_d;
-  int *fail_d;
-  M3X_HIP_CHECK(hipMalloc(&sigs_d, n * 96));
-  M3X_HIP_CHECK(hipMalloc(&out_d, 96));
-  M3X_HIP_CHECK(hipMalloc(&fail_d, 4));
-  hipError_t e1 = hipMemcpyAsync(sigs_d, sigs, n * 96,
-                                 hipMemcpyHostToDevice, ctx->stream);
-  (void)hipMemsetAsync(fail_d, 0, 4, ctx->stream);
+  m3x::DevTemps tmp(ctx->stream);
+  const uint8_t *sigs_d = tmp.upload(sigs, n * 96);
+  uint8_t *out_d = tmp.alloc(96);
+  int *fail_d = tmp.alloc<int>(4);
+  if (!tmp.ok()) return M3X_ERR_HIP;
+  M3X_HIP_CHECK(hipMemsetAsync(fail_d, 0, 4, ctx->stream));
   hipLaunchKernelGGL(k_bls_sig_aggregate_w, dim3(1), dim3(64), 0, ctx->stream,
                      sigs_d, n, out_d, fail_d);
   int fail = 1;
-  (void)hipMemcpyAsync(out_sig, out_d, 96, hipMemcpyDeviceToHost, ctx->stream);
-  (void)hipMemcpyAsync(&fail, fail_d, 4, hipMemcpyDeviceToHost, ctx->stream);
-  hipError_t e2 = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(sigs_d);
-  (void)hipFree(out_d);
-  (void)hipFree(fail_d);
-  if (e1 != hipSuccess || e2 != hipSuccess) return M3X_ERR_HIP;
+  tmp.download(out_sig, out_d, 96);
+  tmp.download(&fail, fail_d, 4);
+  if (!tmp.sync()) return M3X_ERR_HIP;
   return fail ? M3X_ERR_ARG : M3X_OK;
 }
 
@@ -1216,38 +840,15 @@ int32_t m3x_bls_verify_sets(m3x_ctx *ctx, const uint8_t *msgs,
   if (n == 0) return 0;
   M3X_HIP_CHECK(hipSetDevice(ctx->device));
   uint64_t nk = pk_offsets[n];
-  // checked uploads + single cleanup path: an infrastructure failure must
-  // surface as M3X_ERR_HIP, never as a "signature invalid" verdict from a
-  // kernel run over stale device memory
-  uint8_t *msgs_d = nullptr, *sigs_d = nullptr, *pks_d = nullptr;
-  uint32_t *offs_d = nullptr;
-  uint64_t *rands_d = nullptr;
-  int32_t rc = M3X_ERR_HIP;
-  if (hipMalloc(&msgs_d, n * 32) != hipSuccess) goto out;
-  if (hipMalloc(&sigs_d, n * 96) != hipSuccess) goto out;
-  if (hipMalloc(&pks_d, nk * 96) != hipSuccess) goto out;
-  if (hipMalloc(&offs_d, (n + 1) * 4) != hipSuccess) goto out;
-  if (hipMalloc(&rands_d, n * 8) != hipSuccess) goto out;
-  if (hipMemcpy(msgs_d, msgs, n * 32, hipMemcpyHostToDevice) != hipSuccess)
-    goto out;
-  if (hipMemcpy(sigs_d, sigs, n * 96, hipMemcpyHostToDevice) != hipSuccess)
-    goto out;
-  if (hipMemcpy(pks_d, pks, nk * 96, hipMemcpyHostToDevice) != hipSuccess)
-    goto out;
-  if (hipMemcpy(offs_d, pk_offsets, (n + 1) * 4, hipMemcpyHostToDevice) !=
-      hipSuccess)
-    goto out;
-  if (hipMemcpy(rands_d, rands, n * 8, hipMemcpyHostToDevice) != hipSuccess)
-    goto out;
-  rc = m3x_bls_verify_sets_dev(ctx, msgs_d, sigs_d, pks_d, offs_d, rands_d,
-                               n);
-out:
-  if (msgs_d) (void)hipFree(msgs_d);
-  if (sigs_d) (void)hipFree(sigs_d);
-  if (pks_d) (void)hipFree(pks_d);
-  if (offs_d) (void)hipFree(offs_d);
-  if (rands_d) (void)hipFree(rands_d);
-  return rc;
+  m3x::DevTemps tmp(ctx->stream);
+  const uint8_t *msgs_d = tmp.upload(msgs, n * 32);
+  const uint8_t *sigs_d = tmp.upload(sigs, n * 96);
+  const uint8_t *pks_d = tmp.upload(pks, nk * 96);
+  const uint32_t *offs_d = tmp.upload(pk_offsets, (n + 1) * 4);
+  const uint64_t *rands_d = tmp.upload(rands, n * 8);
+  if (!tmp.ok()) return M3X_ERR_HIP;
+  return m3x_bls_verify_sets_dev(ctx, msgs_d, sigs_d, pks_d, offs_d, rands_d,
+                                 n);
 }
 
 } // extern "C"

@@ -74,4 +74,88 @@ void time_end_s(m3x_ctx *ctx, int k, hipStream_t st);
 namespace m3x {
 // ensure scratch buffer has at least `bytes`; returns 0 or M3X_ERR_*
 int ensure_scratch(m3x_ctx *ctx, uint8_t **buf, uint64_t *cur, uint64_t bytes);
+
+// Carves one scratch buffer into 256-byte-aligned pieces. A layout is
+// written once, as a function of the carver: with a null base take() only
+// advances the offset (sizing pass), over the real buffer it returns the
+// pointers.
+struct ScratchCarver {
+  uint8_t *base;
+  uint64_t off = 0;
+  template <typename T> T *take(uint64_t count) {
+    uint64_t at = off;
+    off += (count * sizeof(T) + 255) & ~255ull;
+    return base ? reinterpret_cast<T *>(base + at) : nullptr;
+  }
+};
+
+// size the layout, grow the scratch buffer to it, then lay it out for real
+template <typename Layout>
+int carve_scratch(m3x_ctx *ctx, uint8_t **buf, uint64_t *cur, Layout layout) {
+  ScratchCarver sizing{nullptr};
+  layout(sizing);
+  int rc = ensure_scratch(ctx, buf, cur, sizing.off);
+  if (rc != 0) return rc;
+  ScratchCarver real{*buf};
+  layout(real);
+  return 0;
+}
+
+// The temporary device buffers of one host-buffer call. The first failed
+// allocation or copy is remembered: ok() turns false and later uploads
+// return null, so an infrastructure failure surfaces as M3X_ERR_HIP and
+// never as a verdict computed over stale device memory. The destructor
+// frees everything, on every return path; a caller whose side streams may
+// still read a buffer synchronises them before it returns.
+class DevTemps {
+ public:
+  explicit DevTemps(hipStream_t st) : st_(st) {}
+  DevTemps(const DevTemps &) = delete;
+  DevTemps &operator=(const DevTemps &) = delete;
+  ~DevTemps() {
+    for (int i = 0; i < n_; i++) (void)hipFree(p_[i]);
+  }
+  bool ok() const { return ok_; }
+  template <typename T = uint8_t> T *alloc(uint64_t bytes) {
+    void *d = nullptr;
+    if (!ok_ || n_ == kCap || hipMalloc(&d, bytes ? bytes : 4) != hipSuccess) {
+      ok_ = false;
+      return nullptr;
+    }
+    p_[n_++] = d;
+    return static_cast<T *>(d);
+  }
+  // device copy of a host buffer; the data is in place on return
+  template <typename T> T *upload(const T *host, uint64_t bytes) {
+    T *d = alloc<T>(bytes);
+    if (d && bytes && hipMemcpy(d, host, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+      ok_ = false;
+      return nullptr;
+    }
+    return d;
+  }
+  // queue a copy back to the host on the call's stream; sync() completes it
+  void download(void *dst, const void *src_dev, uint64_t bytes) {
+    if (ok_ && hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToHost, st_) != hipSuccess)
+      ok_ = false;
+  }
+  // wait for the stream (always: buffers are about to be freed)
+  bool sync() {
+    if (hipStreamSynchronize(st_) != hipSuccess) ok_ = false;
+    return ok_;
+  }
+  // hand a buffer over to the caller: the destructor leaves it alone
+  template <typename T> T *release(T *d) {
+    for (int i = 0; i < n_; i++)
+      if (p_[i] == d) p_[i] = p_[--n_];
+    return d;
+  }
+
+ private:
+  static constexpr int kCap = 8;
+  hipStream_t st_;
+  void *p_[kCap] = {};
+  int n_ = 0;
+  bool ok_ = true;
+};
 } // namespace m3x

@@ -72,12 +72,6 @@ __device__ __forceinline__ uint32_t ld_be32(const uint8_t *p) {
   return __builtin_bswap32(v);
 }
 
-__device__ __forceinline__ void g1j_set_inf(g1j &p) {
-  fp_zero(p.x);
-  fp_zero(p.y);
-  fp_zero(p.z);
-}
-
 // Jacobian -> 48-byte compressed form, the inverse of g1_decompress: the
 // sign bit follows the same lexicographic rule, infinity is 0xc0 00...
 __device__ inline void g1_compress(uint8_t *out, const g1j &p) {
@@ -158,11 +152,70 @@ __device__ __forceinline__ uint32_t bitrev_lo(uint32_t v, int bits) {
   return __builtin_bitreverse32(v) >> (32 - bits);
 }
 
-// evaluate_polynomial_in_evaluation_form: one block per blob, thread t owns
-// elements 16t..16t+15. bitrev12(16t+k) = bitrev4(k)<<8 | bitrev8(t), so the
-// thread's roots are omega^bitrev8(t) * (omega^256)^bitrev4(k): one 8-bit
-// power and 15 multiplies, no table. The 16 denominators z - omega_j share
-// one Fermat inversion (Montgomery's trick).
+// A thread's walk over the evaluation domain: of a blob's 256 threads,
+// thread t owns elements 16t..16t+15. bitrev12(16t+k) = bitrev4(k)<<8 |
+// bitrev8(t), so the thread's roots are omega^bitrev8(t) *
+// (omega^256)^bitrev4(k): one 8-bit power and 15 multiplies, no table.
+// Step mi visits k = bitrev4(mi), which makes the second factor
+// (omega^256)^mi, one multiply per step.
+struct DomainWalk {
+  fr w16, base, g;
+  uint32_t first;
+  __device__ __forceinline__ void init(int t) {
+    fr omega;
+#pragma unroll
+    for (int i = 0; i < 8; i++) omega.v[i] = FR_OMEGA_MONT[i];
+    w16 = omega;
+    for (int i = 0; i < 8; i++) fr_sqr(w16, w16); // omega^256
+    uint32_t e = bitrev_lo((uint32_t)t, 8);
+    fr_pow(base, omega, &e, 1);
+    fr_one(g);
+    first = 16u * (uint32_t)t;
+  }
+  // the element step mi visits
+  __device__ __forceinline__ uint32_t index(int mi) const {
+    return first + bitrev_lo((uint32_t)mi, 4);
+  }
+  // steps mi = 0..15 in order: the element j and wk = omega^bitrev12(j)
+  __device__ __forceinline__ uint32_t next(int mi, fr &wk) {
+    fr_mul(wk, base, g);
+    fr_mul(g, g, w16);
+    return index(mi);
+  }
+};
+
+// Montgomery's trick for a thread's 16 denominators: push() them in order,
+// one Fermat inversion, then pop() hands the inverses back last to first.
+// The running product is the caller's local: as a member it would stay in
+// scratch memory with the arrays (32 B more per lane, measurably slower).
+struct BatchInv16 {
+  fr den[16], pre[16];
+  __device__ __forceinline__ void init(fr &run) { fr_one(run); }
+  __device__ __forceinline__ void push(fr &run, int mi, const fr &d) {
+    den[mi] = d;
+    fr_mul(run, run, d);
+    pre[mi] = run;
+  }
+  __device__ __forceinline__ void invert(fr &run) { fr_inv(run, run); }
+  // id = 1/den[mi]; call for mi = 15 down to 0
+  __device__ __forceinline__ void pop(fr &run, int mi, fr &id) {
+    if (mi > 0)
+      fr_mul(id, run, pre[mi - 1]);
+    else
+      id = run;
+    fr_mul(run, run, den[mi]);
+  }
+};
+
+struct fr_add_op {
+  __device__ __forceinline__ void operator()(fr &r, const fr &a,
+                                             const fr &b) const {
+    fr_add(r, a, b);
+  }
+};
+
+// evaluate_polynomial_in_evaluation_form: one block per blob, 16 elements
+// per thread; the 16 denominators z - omega_j share one inversion.
 __global__ __launch_bounds__(256) void k_kzg_eval(
     const uint8_t *__restrict__ blobs, uint64_t n, KzgWork w) {
   __shared__ fr lds[256];
@@ -179,28 +232,20 @@ __global__ __launch_bounds__(256) void k_kzg_eval(
     if (t == 0) atomicOr(w.fail, 1);
     return;
   }
-  fr omega, w16, base;
-#pragma unroll
-  for (int i = 0; i < 8; i++) omega.v[i] = FR_OMEGA_MONT[i];
-  w16 = omega;
-  for (int i = 0; i < 8; i++) fr_sqr(w16, w16); // omega^256
-  uint32_t e = bitrev_lo((uint32_t)t, 8);
-  fr_pow(base, omega, &e, 1);
-  fr num[16], den[16], pre[16];
-  fr g, run;
-  fr_one(g);
-  fr_one(run);
+  DomainWalk dw;
+  BatchInv16 bi;
+  dw.init(t);
+  fr run;
+  bi.init(run);
+  fr num[16];
   bool bad = false;
   for (int mi = 0; mi < 16; mi++) {
-    int k = (int)bitrev_lo((uint32_t)mi, 4);
-    uint32_t j = 16u * (uint32_t)t + (uint32_t)k;
     fr f, wk, d;
+    uint32_t j = dw.next(mi, wk);
     if (!fr_from_be32(f, blob + 32 * j)) {
       bad = true;
       fr_zero(f);
     }
-    fr_mul(wk, base, g); // omega^bitrev12(j)
-    fr_mul(g, g, w16);
     fr_sub(d, z, wk);
     if (fr_is_zero(d)) { // z is in the domain: y = f_j, no division
       s_hitval = f;
@@ -208,34 +253,20 @@ __global__ __launch_bounds__(256) void k_kzg_eval(
       fr_one(d);
     }
     fr_mul(num[mi], f, wk);
-    den[mi] = d;
-    fr_mul(run, run, d);
-    pre[mi] = run;
+    bi.push(run, mi, d);
   }
   if (bad) atomicOr(w.fail, 1);
-  fr inv, acc;
-  fr_inv(inv, run);
+  fr acc;
+  bi.invert(run);
   fr_zero(acc);
   for (int mi = 15; mi >= 0; mi--) {
     fr id, term;
-    if (mi > 0)
-      fr_mul(id, inv, pre[mi - 1]);
-    else
-      id = inv;
-    fr_mul(inv, inv, den[mi]);
+    bi.pop(run, mi, id);
     fr_mul(term, num[mi], id);
     fr_add(acc, acc, term);
   }
   lds[t] = acc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (t < s) {
-      fr a;
-      fr_add(a, lds[t], lds[t + s]);
-      lds[t] = a;
-    }
-    __syncthreads();
-  }
+  block_tree_reduce<fr, 256>(lds, t, fr_add_op{});
   if (t == 0) {
     fr y;
     if (s_hit) {
@@ -314,20 +345,7 @@ __global__ __launch_bounds__(256) void k_kzg_batch_r(
 // validate_kzg_g1: decompress (infinity is a valid KZG point, unlike a
 // public key) + subgroup check as in k_bls_pk_decompress
 __device__ inline bool kzg_validate_g1(g1a &p, const uint8_t *src) {
-  bool ok = g1_decompress(p, src) == 0;
-  if (ok && !p.inf) {
-    uint8_t be[32];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      uint64_t limb = BLS_ORDER[3 - i];
-#pragma unroll
-      for (int j = 0; j < 8; j++) be[8 * i + j] = (uint8_t)(limb >> (56 - 8 * j));
-    }
-    g1j t;
-    g1j_mul_be(t, p, be, 32);
-    ok = g1j_is_inf(t);
-  }
-  return ok;
+  return g1_decompress(p, src) == 0 && (p.inf || g1_in_subgroup(p));
 }
 
 // validate_kzg_g1 for every commitment and proof. One lane per point.
@@ -393,30 +411,15 @@ __global__ __launch_bounds__(64, 1) void k_kzg_mults(uint64_t n, KzgWork w) {
   w.terms[lane] = out;
 }
 
-// two-stage Jacobian G1 sum (k_bls_reduce_sig's shape)
+// two-stage Jacobian G1 sum (block_span_reduce, as k_bls_reduce_sig); a
+// failed call skips the work
 __global__ __launch_bounds__(256) void k_kzg_reduce_g1(
     const g1j *__restrict__ in, uint64_t n, g1j *__restrict__ out,
     const int *__restrict__ fail) {
   __shared__ g1j lds[256];
   if (*fail) return;
-  uint64_t per = (n + gridDim.x - 1) / gridDim.x;
-  uint64_t lo = (uint64_t)blockIdx.x * per;
-  uint64_t hi = lo + per < n ? lo + per : n;
-  g1j local;
-  g1j_set_inf(local);
-  for (uint64_t i = lo + threadIdx.x; i < hi; i += 256)
-    g1j_add(local, local, in[i]);
-  lds[threadIdx.x] = local;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      g1j t;
-      g1j_add(t, lds[threadIdx.x], lds[threadIdx.x + s]);
-      lds[threadIdx.x] = t;
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[blockIdx.x] = lds[0];
+  block_span_reduce<g1j, 256>(in, n, out, lds, g1j_add_op{},
+                              [](g1j &r) { g1j_set_inf(r); });
 }
 
 // the pairing check, one wave (k_bls_finish's shape). miller_w returns one
@@ -463,57 +466,54 @@ __global__ void k_kzg_setup(const uint8_t *__restrict__ tau96,
 // ------------------------------------------------------------------- host
 
 int kzg_layout(m3x_ctx *ctx, uint64_t n, KzgWork &w) {
-  uint64_t bytes = 0;
-  auto align = [](uint64_t x) { return (x + 255) & ~255ull; };
-  uint64_t off_zs = bytes; bytes += align(n * 32);
-  uint64_t off_ys = bytes; bytes += align(n * 32);
-  uint64_t off_tr = bytes; bytes += align(32 + 160 * n);
-  uint64_t off_sc = bytes; bytes += align((2 * n + 1) * 32);
-  uint64_t off_r = bytes; bytes += 256;
-  uint64_t off_pts = bytes; bytes += align(2 * n * sizeof(g1j));
-  uint64_t off_terms = bytes; bytes += align((3 * n + 1) * sizeof(g1j));
-  uint64_t off_stage = bytes; bytes += align(512 * sizeof(g1j));
-  uint64_t off_sums = bytes; bytes += align(2 * sizeof(g1j));
-  uint64_t off_fail = bytes; bytes += 256;
-  uint64_t off_v = bytes; bytes += 256;
-  int rc = m3x::ensure_scratch(ctx, &ctx->scratch_a, &ctx->scratch_a_bytes,
-                               bytes);
-  if (rc != M3X_OK) return rc;
-  uint8_t *base = ctx->scratch_a;
-  w.zs = base + off_zs;
-  w.ys = base + off_ys;
-  w.tr = base + off_tr;
-  w.sc = base + off_sc;
-  w.r_out = base + off_r;
-  w.pts = reinterpret_cast<g1j *>(base + off_pts);
-  w.terms = reinterpret_cast<g1j *>(base + off_terms);
-  w.stage = reinterpret_cast<g1j *>(base + off_stage);
-  w.sums = reinterpret_cast<g1j *>(base + off_sums);
-  w.fail = reinterpret_cast<int *>(base + off_fail);
-  w.verdict = reinterpret_cast<int *>(base + off_v);
+  return m3x::carve_scratch(
+      ctx, &ctx->scratch_a, &ctx->scratch_a_bytes, [&](m3x::ScratchCarver &c) {
+        w.zs = c.take<uint8_t>(n * 32);
+        w.ys = c.take<uint8_t>(n * 32);
+        w.tr = c.take<uint8_t>(32 + 160 * n);
+        w.sc = c.take<uint8_t>((2 * n + 1) * 32);
+        w.r_out = c.take<uint8_t>(32);
+        w.pts = c.take<g1j>(2 * n);
+        w.terms = c.take<g1j>(3 * n + 1);
+        w.stage = c.take<g1j>(512);
+        w.sums = c.take<g1j>(2);
+        w.fail = c.take<int>(1);
+        w.verdict = c.take<int>(1);
+      });
+}
+
+// the per-blob challenge hash, on stream2; ev_s2 marks its end
+int launch_challenge(m3x_ctx *ctx, const KzgWork &w, const uint8_t *blobs_dev,
+                     const uint8_t *cs_dev, uint64_t n) {
+  m3x::time_begin_s(ctx, M3X_K_KZG_CHALLENGE, ctx->stream2);
+  hipLaunchKernelGGL(k_kzg_challenge, dim3((uint32_t)((n + 63) / 64)),
+                     dim3(64), 0, ctx->stream2, blobs_dev, cs_dev, n, w);
+  m3x::time_end_s(ctx, M3X_K_KZG_CHALLENGE, ctx->stream2);
+  M3X_HIP_CHECK(hipEventRecord(ctx->ev_s2, ctx->stream2));
   return M3X_OK;
 }
 
-// challenge (stream2) + evaluation; zs_dev != nullptr supplies explicit z
-int launch_challenge_eval(m3x_ctx *ctx, const KzgWork &w,
-                          const uint8_t *blobs_dev, const uint8_t *cs_dev,
-                          const uint8_t *zs_dev, uint64_t n) {
-  if (zs_dev) {
-    M3X_HIP_CHECK(hipMemcpyAsync(w.zs, zs_dev, n * 32,
-                                 hipMemcpyDeviceToDevice, ctx->stream));
-  } else {
-    m3x::time_begin_s(ctx, M3X_K_KZG_CHALLENGE, ctx->stream2);
-    hipLaunchKernelGGL(k_kzg_challenge, dim3((uint32_t)((n + 63) / 64)),
-                       dim3(64), 0, ctx->stream2, blobs_dev, cs_dev, n, w);
-    m3x::time_end_s(ctx, M3X_K_KZG_CHALLENGE, ctx->stream2);
-    M3X_HIP_CHECK(hipEventRecord(ctx->ev_s2, ctx->stream2));
-    M3X_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->ev_s2, 0));
-  }
+// the evaluation, on the main stream; hashed = true waits for the challenge
+int launch_eval(m3x_ctx *ctx, const KzgWork &w, const uint8_t *blobs_dev,
+                uint64_t n, bool hashed) {
+  if (hashed) M3X_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->ev_s2, 0));
   m3x::time_begin(ctx, M3X_K_KZG_EVAL);
   hipLaunchKernelGGL(k_kzg_eval, dim3((uint32_t)n), dim3(256), 0, ctx->stream,
                      blobs_dev, n, w);
   m3x::time_end(ctx, M3X_K_KZG_EVAL);
   return M3X_OK;
+}
+
+// challenge + evaluation; zs_dev != nullptr supplies explicit z
+int launch_challenge_eval(m3x_ctx *ctx, const KzgWork &w,
+                          const uint8_t *blobs_dev, const uint8_t *cs_dev,
+                          const uint8_t *zs_dev, uint64_t n) {
+  if (zs_dev)
+    M3X_HIP_CHECK(hipMemcpyAsync(w.zs, zs_dev, n * 32,
+                                 hipMemcpyDeviceToDevice, ctx->stream));
+  else if (int rc = launch_challenge(ctx, w, blobs_dev, cs_dev, n))
+    return rc;
+  return launch_eval(ctx, w, blobs_dev, n, !zs_dev);
 }
 
 // blobs_dev != nullptr: blob batch (z, y computed on the device);
@@ -530,11 +530,8 @@ int run_kzg(m3x_ctx *ctx, m3x_kzg *kzg, const uint8_t *blobs_dev,
   // point validation does not depend on z: it runs on the main stream
   // while the serial challenge hash runs on stream2
   if (blobs_dev) {
-    m3x::time_begin_s(ctx, M3X_K_KZG_CHALLENGE, ctx->stream2);
-    hipLaunchKernelGGL(k_kzg_challenge, dim3((uint32_t)((n + 63) / 64)),
-                       dim3(64), 0, ctx->stream2, blobs_dev, cs_dev, n, w);
-    m3x::time_end_s(ctx, M3X_K_KZG_CHALLENGE, ctx->stream2);
-    M3X_HIP_CHECK(hipEventRecord(ctx->ev_s2, ctx->stream2));
+    rc = launch_challenge(ctx, w, blobs_dev, cs_dev, n);
+    if (rc != M3X_OK) return rc;
   } else {
     M3X_HIP_CHECK(hipMemcpyAsync(w.zs, zs_dev, n * 32,
                                  hipMemcpyDeviceToDevice, ctx->stream));
@@ -546,11 +543,8 @@ int run_kzg(m3x_ctx *ctx, m3x_kzg *kzg, const uint8_t *blobs_dev,
                      cs_dev, proofs_dev, n, w);
   m3x::time_end(ctx, M3X_K_KZG_DECOMP);
   if (blobs_dev) {
-    M3X_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->ev_s2, 0));
-    m3x::time_begin(ctx, M3X_K_KZG_EVAL);
-    hipLaunchKernelGGL(k_kzg_eval, dim3((uint32_t)n), dim3(256), 0,
-                       ctx->stream, blobs_dev, n, w);
-    m3x::time_end(ctx, M3X_K_KZG_EVAL);
+    rc = launch_eval(ctx, w, blobs_dev, n, true);
+    if (rc != M3X_OK) return rc;
   }
   m3x::time_begin(ctx, M3X_K_KZG_BATCH_R);
   hipLaunchKernelGGL(k_kzg_batch_r, dim3(1), dim3(256), 0, ctx->stream,
@@ -590,17 +584,6 @@ int run_kzg(m3x_ctx *ctx, m3x_kzg *kzg, const uint8_t *blobs_dev,
   if (fail) return M3X_ERR_ENCODING;
   *out = verdict;
   return M3X_OK;
-}
-
-// upload helper: device copy of a host buffer (nullptr on failure)
-uint8_t *dev_copy(const uint8_t *host, uint64_t bytes) {
-  uint8_t *d = nullptr;
-  if (hipMalloc(&d, bytes ? bytes : 4) != hipSuccess) return nullptr;
-  if (bytes && hipMemcpy(d, host, bytes, hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(d);
-    return nullptr;
-  }
-  return d;
 }
 
 bool kzg_args_ok(m3x_ctx *ctx, m3x_kzg *kzg, uint64_t n) {
@@ -706,25 +689,17 @@ __global__ __launch_bounds__(256) void k_kzgp_quotient(
   // a non-canonical z or y was flagged by k_kzg_eval; the call has failed
   if (!fr_from_be32(z, w.zs + 32 * b)) fr_zero(z);
   if (!fr_from_be32(y, w.ys + 32 * b)) fr_zero(y);
-  fr omega, w16, base;
-#pragma unroll
-  for (int i = 0; i < 8; i++) omega.v[i] = FR_OMEGA_MONT[i];
-  w16 = omega;
-  for (int i = 0; i < 8; i++) fr_sqr(w16, w16); // omega^256
-  uint32_t e = bitrev_lo((uint32_t)t, 8);
-  fr_pow(base, omega, &e, 1);
-  fr num[16], den[16], pre[16];
-  fr g, run;
-  fr_one(g);
-  fr_one(run);
+  DomainWalk dw;
+  BatchInv16 bi;
+  dw.init(t);
+  fr run;
+  bi.init(run);
+  fr num[16];
   int hit = -1;
   for (int mi = 0; mi < 16; mi++) {
-    int k = (int)bitrev_lo((uint32_t)mi, 4);
-    uint32_t j = 16u * (uint32_t)t + (uint32_t)k;
     fr f, wk, d;
+    uint32_t j = dw.next(mi, wk);
     if (!fr_from_be32(f, blob + 32 * j)) fr_zero(f); // flagged by k_kzg_eval
-    fr_mul(wk, base, g); // omega^bitrev12(j)
-    fr_mul(g, g, w16);
     fr_sub(d, wk, z);
     fr_sub(num[mi], f, y);
     if (fr_is_zero(d)) { // z = w_j: this element takes the in-domain term
@@ -732,39 +707,23 @@ __global__ __launch_bounds__(256) void k_kzgp_quotient(
       hit = mi;
       fr_one(d);
     }
-    den[mi] = d;
-    fr_mul(run, run, d);
-    pre[mi] = run;
+    bi.push(run, mi, d);
   }
-  fr inv, acc;
-  fr_inv(inv, run);
+  fr acc;
+  bi.invert(run);
   fr_zero(acc);
   for (int mi = 15; mi >= 0; mi--) {
-    int k = (int)bitrev_lo((uint32_t)mi, 4);
-    uint32_t j = 16u * (uint32_t)t + (uint32_t)k;
     fr id, q, wk, term;
-    if (mi > 0)
-      fr_mul(id, inv, pre[mi - 1]);
-    else
-      id = inv;
-    fr_mul(inv, inv, den[mi]);
+    bi.pop(run, mi, id);
     if (mi == hit) continue;
     fr_mul(q, num[mi], id);
-    fr_to_be32(q, q_out + 32 * j);
-    fr_add(wk, den[mi], z);
+    fr_to_be32(q, q_out + 32 * dw.index(mi));
+    fr_add(wk, bi.den[mi], z);
     fr_mul(term, q, wk);
     fr_add(acc, acc, term);
   }
   lds[t] = acc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (t < s) {
-      fr a;
-      fr_add(a, lds[t], lds[t + s]);
-      lds[t] = a;
-    }
-    __syncthreads();
-  }
+  block_tree_reduce<fr, 256>(lds, t, fr_add_op{});
   if (t == 0 && s_m >= 0) {
     fr zi, q;
     fr_inv(zi, z); // z is a root of unity here, never zero
@@ -832,15 +791,7 @@ __global__ __launch_bounds__(256) void k_kzgp_msm(
     g1j_add_aff(acc, acc, pt);
   }
   lds[t] = acc;
-  __syncthreads();
-  for (uint32_t st = 128; st > 0; st >>= 1) {
-    if (t < st) {
-      g1j sum;
-      g1j_add(sum, lds[t], lds[t + st]);
-      lds[t] = sum;
-    }
-    __syncthreads();
-  }
+  block_tree_reduce<g1j, 256>(lds, (int)t, g1j_add_op{});
   if (t == 0) partial[blob * KZGP_BLOCKS + blockIdx.x] = lds[0];
 }
 
@@ -851,15 +802,7 @@ __global__ __launch_bounds__(KZGP_BLOCKS) void k_kzgp_finish(
   uint32_t t = threadIdx.x;
   uint64_t blob = blockIdx.x;
   lds[t] = partial[blob * KZGP_BLOCKS + t];
-  __syncthreads();
-  for (uint32_t st = KZGP_BLOCKS / 2; st > 0; st >>= 1) {
-    if (t < st) {
-      g1j sum;
-      g1j_add(sum, lds[t], lds[t + st]);
-      lds[t] = sum;
-    }
-    __syncthreads();
-  }
+  block_tree_reduce<g1j, KZGP_BLOCKS>(lds, (int)t, g1j_add_op{});
   if (t == 0) g1_compress(out + 48 * blob, lds[0]);
 }
 
@@ -878,14 +821,11 @@ struct KzgpWork {
 };
 
 int kzgp_layout(m3x_ctx *ctx, uint64_t n, bool quotient, KzgpWork &p) {
-  uint64_t part = (n * KZGP_BLOCKS * sizeof(g1j) + 255) & ~255ull;
-  uint64_t bytes = part + (quotient ? n * KZG_BLOB_BYTES : 0);
-  int rc = m3x::ensure_scratch(ctx, &ctx->scratch_b, &ctx->scratch_b_bytes,
-                               bytes);
-  if (rc != M3X_OK) return rc;
-  p.partial = reinterpret_cast<g1j *>(ctx->scratch_b);
-  p.qs = ctx->scratch_b + part;
-  return M3X_OK;
+  return m3x::carve_scratch(
+      ctx, &ctx->scratch_b, &ctx->scratch_b_bytes, [&](m3x::ScratchCarver &c) {
+        p.partial = c.take<g1j>(n * KZGP_BLOCKS);
+        p.qs = c.take<uint8_t>(quotient ? n * KZG_BLOB_BYTES : 0);
+      });
 }
 
 bool kzgp_args_ok(m3x_ctx *ctx, m3x_kzg *kzg, uint64_t n) {
@@ -926,29 +866,6 @@ int kzgp_wait(m3x_ctx *ctx, const KzgWork &w) {
   return fail ? M3X_ERR_ENCODING : M3X_OK;
 }
 
-// run a *_dev entry over host buffers: ins[i] (in_bytes[i]) are uploaded,
-// outs[i] (out_bytes[i]) downloaded after a successful call
-template <typename F>
-int32_t kzgp_host_call(const uint8_t *const *ins, const uint64_t *in_bytes,
-                       int n_in, uint8_t *const *outs,
-                       const uint64_t *out_bytes, int n_out, F call) {
-  uint8_t *d[6] = {};
-  int32_t rc = M3X_ERR_HIP;
-  bool ok = true;
-  for (int i = 0; i < n_in && ok; i++)
-    ok = (d[i] = dev_copy(ins[i], in_bytes[i])) != nullptr;
-  for (int i = 0; i < n_out && ok; i++)
-    ok = hipMalloc(&d[n_in + i], out_bytes[i]) == hipSuccess;
-  if (ok) rc = call(d);
-  for (int i = 0; i < n_out && rc == M3X_OK; i++)
-    if (hipMemcpy(outs[i], d[n_in + i], out_bytes[i],
-                  hipMemcpyDeviceToHost) != hipSuccess)
-      rc = M3X_ERR_HIP;
-  for (int i = 0; i < n_in + n_out; i++)
-    if (d[i]) (void)hipFree(d[i]);
-  return rc;
-}
-
 } // namespace
 
 extern "C" {
@@ -958,34 +875,20 @@ int32_t m3x_kzg_create(m3x_ctx *ctx, const uint8_t g2_tau[96],
   if (!ctx || !g2_tau || !out) return M3X_ERR_ARG;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   M3X_HIP_CHECK(hipSetDevice(ctx->device));
-  g2j *g2 = nullptr;
-  uint8_t *tau_d = nullptr;
-  int *fail_d = nullptr;
-  int fail = 1;
-  int32_t rc = M3X_ERR_HIP;
-  if (hipMalloc(&g2, 2 * sizeof(g2j)) != hipSuccess) goto out;
-  if (hipMalloc(&tau_d, 96) != hipSuccess) goto out;
-  if (hipMalloc(&fail_d, 4) != hipSuccess) goto out;
-  if (hipMemcpyAsync(tau_d, g2_tau, 96, hipMemcpyHostToDevice, ctx->stream) !=
-      hipSuccess)
-    goto out;
+  m3x::DevTemps tmp(ctx->stream);
+  g2j *g2 = tmp.alloc<g2j>(2 * sizeof(g2j));
+  const uint8_t *tau_d = tmp.upload(g2_tau, 96);
+  int *fail_d = tmp.alloc<int>(4);
+  if (!tmp.ok()) return M3X_ERR_HIP;
   hipLaunchKernelGGL(k_kzg_setup, dim3(1), dim3(1), 0, ctx->stream, tau_d, g2,
                      fail_d);
-  if (hipMemcpyAsync(&fail, fail_d, 4, hipMemcpyDeviceToHost, ctx->stream) !=
-      hipSuccess)
-    goto out;
-  if (hipStreamSynchronize(ctx->stream) != hipSuccess) goto out;
-  rc = fail ? M3X_ERR_ENCODING : M3X_OK;
-out:
-  if (tau_d) (void)hipFree(tau_d);
-  if (fail_d) (void)hipFree(fail_d);
-  if (rc != M3X_OK) {
-    if (g2) (void)hipFree(g2);
-    return rc;
-  }
+  int fail = 1;
+  tmp.download(&fail, fail_d, 4);
+  if (!tmp.sync()) return M3X_ERR_HIP;
+  if (fail) return M3X_ERR_ENCODING;
   auto *k = new m3x_kzg();
   k->device = ctx->device;
-  k->g2 = g2;
+  k->g2 = tmp.release(g2); // the handle owns it from here
   *out = k;
   return M3X_OK;
 }
@@ -1005,45 +908,24 @@ int32_t m3x_kzgp_load_g1_lagrange(m3x_ctx *ctx, m3x_kzg *kzg,
     return M3X_ERR_ARG;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   M3X_HIP_CHECK(hipSetDevice(ctx->device));
-  uint8_t *lag_d = dev_copy(g1_lagrange, (uint64_t)KZG_N * 48);
-  g1j *bases = nullptr;
-  g1t *table = nullptr;
-  int *fail_d = nullptr;
-  int fail = 1;
-  int32_t rc = M3X_ERR_HIP;
-  if (!lag_d) goto out;
-  if (hipMalloc(&fail_d, 4) != hipSuccess) goto out;
-  rc = M3X_ERR_NOMEM;
-  if (hipMalloc(&bases, (uint64_t)KZGP_WINDOWS * KZG_N * sizeof(g1j)) !=
-      hipSuccess)
-    goto out;
-  if (hipMalloc(&table, KZGP_TABLE_POINTS * sizeof(g1t)) != hipSuccess)
-    goto out;
-  rc = M3X_ERR_HIP;
-  if (hipMemsetAsync(fail_d, 0, 4, ctx->stream) != hipSuccess) goto out;
+  m3x::DevTemps tmp(ctx->stream);
+  const uint8_t *lag_d = tmp.upload(g1_lagrange, (uint64_t)KZG_N * 48);
+  int *fail_d = tmp.alloc<int>(4);
+  if (!tmp.ok()) return M3X_ERR_HIP;
+  g1j *bases = tmp.alloc<g1j>((uint64_t)KZGP_WINDOWS * KZG_N * sizeof(g1j));
+  g1t *table = tmp.alloc<g1t>(KZGP_TABLE_POINTS * sizeof(g1t));
+  if (!tmp.ok()) return M3X_ERR_NOMEM;
+  M3X_HIP_CHECK(hipMemsetAsync(fail_d, 0, 4, ctx->stream));
   hipLaunchKernelGGL(k_kzgp_bases, dim3(KZG_N / 64), dim3(64), 0, ctx->stream,
                      lag_d, bases, fail_d);
-  if (hipMemcpyAsync(&fail, fail_d, 4, hipMemcpyDeviceToHost, ctx->stream) !=
-      hipSuccess)
-    goto out;
-  if (hipStreamSynchronize(ctx->stream) != hipSuccess) goto out;
-  if (fail) {
-    rc = M3X_ERR_ENCODING;
-    goto out;
-  }
+  int fail = 1;
+  tmp.download(&fail, fail_d, 4);
+  if (!tmp.sync()) return M3X_ERR_HIP;
+  if (fail) return M3X_ERR_ENCODING;
   hipLaunchKernelGGL(k_kzgp_table, dim3(KZGP_WINDOWS * KZG_N / 64), dim3(64),
                      0, ctx->stream, bases, table);
-  if (hipStreamSynchronize(ctx->stream) != hipSuccess) goto out;
-  rc = M3X_OK;
-out:
-  if (lag_d) (void)hipFree(lag_d);
-  if (fail_d) (void)hipFree(fail_d);
-  if (bases) (void)hipFree(bases);
-  if (rc != M3X_OK) {
-    if (table) (void)hipFree(table);
-    return rc;
-  }
-  kzg->table = table;
+  if (!tmp.sync()) return M3X_ERR_HIP;
+  kzg->table = tmp.release(table); // the handle owns it from here
   return M3X_OK;
 }
 
@@ -1075,15 +957,14 @@ int32_t m3x_kzgp_blob_to_commitment(m3x_ctx *ctx, m3x_kzg *kzg,
   if (!blobs || !out) return M3X_ERR_ARG;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   M3X_HIP_CHECK(hipSetDevice(ctx->device));
-  const uint8_t *ins[1] = {blobs};
-  uint64_t in_bytes[1] = {n * KZG_BLOB_BYTES};
-  uint8_t *outs[1] = {out};
-  uint64_t out_bytes[1] = {n * 48};
-  return kzgp_host_call(ins, in_bytes, 1, outs, out_bytes, 1,
-                        [&](uint8_t **d) {
-                          return m3x_kzgp_blob_to_commitment_dev(ctx, kzg, d[0],
-                                                                 n, d[1]);
-                        });
+  m3x::DevTemps tmp(ctx->stream);
+  const uint8_t *bl_d = tmp.upload(blobs, n * KZG_BLOB_BYTES);
+  uint8_t *out_d = tmp.alloc(n * 48);
+  if (!tmp.ok()) return M3X_ERR_HIP;
+  int32_t rc = m3x_kzgp_blob_to_commitment_dev(ctx, kzg, bl_d, n, out_d);
+  if (rc != M3X_OK) return rc;
+  tmp.download(out, out_d, n * 48);
+  return tmp.sync() ? M3X_OK : M3X_ERR_HIP;
 }
 
 int32_t m3x_kzgp_compute_proof_dev(m3x_ctx *ctx, m3x_kzg *kzg,
@@ -1121,16 +1002,16 @@ int32_t m3x_kzgp_compute_proof(m3x_ctx *ctx, m3x_kzg *kzg,
   if (!blobs || !zs || !proofs_out || !ys_out) return M3X_ERR_ARG;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   M3X_HIP_CHECK(hipSetDevice(ctx->device));
-  const uint8_t *ins[2] = {blobs, zs};
-  uint64_t in_bytes[2] = {n * KZG_BLOB_BYTES, n * 32};
-  uint8_t *outs[2] = {proofs_out, ys_out};
-  uint64_t out_bytes[2] = {n * 48, n * 32};
-  return kzgp_host_call(ins, in_bytes, 2, outs, out_bytes, 2,
-                        [&](uint8_t **d) {
-                          return m3x_kzgp_compute_proof_dev(ctx, kzg, d[0],
-                                                            d[1], n, d[2],
-                                                            d[3]);
-                        });
+  m3x::DevTemps tmp(ctx->stream);
+  const uint8_t *bl_d = tmp.upload(blobs, n * KZG_BLOB_BYTES);
+  const uint8_t *zs_d = tmp.upload(zs, n * 32);
+  uint8_t *pr_d = tmp.alloc(n * 48), *ys_d = tmp.alloc(n * 32);
+  if (!tmp.ok()) return M3X_ERR_HIP;
+  int32_t rc = m3x_kzgp_compute_proof_dev(ctx, kzg, bl_d, zs_d, n, pr_d, ys_d);
+  if (rc != M3X_OK) return rc;
+  tmp.download(proofs_out, pr_d, n * 48);
+  tmp.download(ys_out, ys_d, n * 32);
+  return tmp.sync() ? M3X_OK : M3X_ERR_HIP;
 }
 
 int32_t m3x_kzgp_compute_blob_proof_dev(m3x_ctx *ctx, m3x_kzg *kzg,
@@ -1179,15 +1060,16 @@ int32_t m3x_kzgp_compute_blob_proof(m3x_ctx *ctx, m3x_kzg *kzg,
   if (!blobs || !cs || !out) return M3X_ERR_ARG;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   M3X_HIP_CHECK(hipSetDevice(ctx->device));
-  const uint8_t *ins[2] = {blobs, cs};
-  uint64_t in_bytes[2] = {n * KZG_BLOB_BYTES, n * 48};
-  uint8_t *outs[1] = {out};
-  uint64_t out_bytes[1] = {n * 48};
-  return kzgp_host_call(ins, in_bytes, 2, outs, out_bytes, 1,
-                        [&](uint8_t **d) {
-                          return m3x_kzgp_compute_blob_proof_dev(
-                              ctx, kzg, d[0], d[1], n, d[2]);
-                        });
+  m3x::DevTemps tmp(ctx->stream);
+  const uint8_t *bl_d = tmp.upload(blobs, n * KZG_BLOB_BYTES);
+  const uint8_t *cs_d = tmp.upload(cs, n * 48);
+  uint8_t *out_d = tmp.alloc(n * 48);
+  if (!tmp.ok()) return M3X_ERR_HIP;
+  // synchronises stream2 and stream3 itself, also when it fails
+  int32_t rc = m3x_kzgp_compute_blob_proof_dev(ctx, kzg, bl_d, cs_d, n, out_d);
+  if (rc != M3X_OK) return rc;
+  tmp.download(out, out_d, n * 48);
+  return tmp.sync() ? M3X_OK : M3X_ERR_HIP;
 }
 
 int32_t m3x_kzg_verify_proof_batch(m3x_ctx *ctx, m3x_kzg *kzg,
@@ -1199,18 +1081,14 @@ int32_t m3x_kzg_verify_proof_batch(m3x_ctx *ctx, m3x_kzg *kzg,
   if (!cs || !zs || !ys || !proofs) return M3X_ERR_ARG;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   M3X_HIP_CHECK(hipSetDevice(ctx->device));
-  uint8_t *cs_d = dev_copy(cs, n * 48), *zs_d = dev_copy(zs, n * 32),
-          *ys_d = dev_copy(ys, n * 32), *pr_d = dev_copy(proofs, n * 48);
-  int32_t rc = M3X_ERR_HIP, verdict = 0;
-  if (cs_d && zs_d && ys_d && pr_d) {
-    rc = run_kzg(ctx, kzg, nullptr, cs_d, zs_d, ys_d, pr_d, n, &verdict);
-    if (rc == M3X_OK) rc = verdict;
-  }
-  if (cs_d) (void)hipFree(cs_d);
-  if (zs_d) (void)hipFree(zs_d);
-  if (ys_d) (void)hipFree(ys_d);
-  if (pr_d) (void)hipFree(pr_d);
-  return rc;
+  m3x::DevTemps tmp(ctx->stream);
+  const uint8_t *cs_d = tmp.upload(cs, n * 48), *zs_d = tmp.upload(zs, n * 32),
+                *ys_d = tmp.upload(ys, n * 32),
+                *pr_d = tmp.upload(proofs, n * 48);
+  if (!tmp.ok()) return M3X_ERR_HIP;
+  int32_t verdict = 0;
+  int32_t rc = run_kzg(ctx, kzg, nullptr, cs_d, zs_d, ys_d, pr_d, n, &verdict);
+  return rc == M3X_OK ? verdict : rc;
 }
 
 int32_t m3x_kzg_verify_proof(m3x_ctx *ctx, m3x_kzg *kzg, const uint8_t c[48],
@@ -1245,15 +1123,12 @@ int32_t m3x_kzg_verify_blob_proof_batch(m3x_ctx *ctx, m3x_kzg *kzg,
   if (!blobs || !cs || !proofs) return M3X_ERR_ARG;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   M3X_HIP_CHECK(hipSetDevice(ctx->device));
-  uint8_t *bl_d = dev_copy(blobs, n * KZG_BLOB_BYTES),
-          *cs_d = dev_copy(cs, n * 48), *pr_d = dev_copy(proofs, n * 48);
-  int32_t rc = M3X_ERR_HIP;
-  if (bl_d && cs_d && pr_d)
-    rc = m3x_kzg_verify_blob_proof_batch_dev(ctx, kzg, bl_d, cs_d, pr_d, n);
-  if (bl_d) (void)hipFree(bl_d);
-  if (cs_d) (void)hipFree(cs_d);
-  if (pr_d) (void)hipFree(pr_d);
-  return rc;
+  m3x::DevTemps tmp(ctx->stream);
+  const uint8_t *bl_d = tmp.upload(blobs, n * KZG_BLOB_BYTES),
+                *cs_d = tmp.upload(cs, n * 48),
+                *pr_d = tmp.upload(proofs, n * 48);
+  if (!tmp.ok()) return M3X_ERR_HIP;
+  return m3x_kzg_verify_blob_proof_batch_dev(ctx, kzg, bl_d, cs_d, pr_d, n);
 }
 
 int32_t m3x_kzg_blob_challenge_eval(m3x_ctx *ctx, const uint8_t *blobs,
@@ -1268,32 +1143,23 @@ int32_t m3x_kzg_blob_challenge_eval(m3x_ctx *ctx, const uint8_t *blobs,
   KzgWork w;
   int32_t rc = kzg_layout(ctx, n, w);
   if (rc != M3X_OK) return rc;
-  uint8_t *bl_d = dev_copy(blobs, n * KZG_BLOB_BYTES),
-          *cs_d = dev_copy(cs, n * 48),
-          *zs_d = zs_in ? dev_copy(zs_in, n * 32) : nullptr;
+  m3x::DevTemps tmp(ctx->stream);
+  const uint8_t *bl_d = tmp.upload(blobs, n * KZG_BLOB_BYTES),
+                *cs_d = tmp.upload(cs, n * 48),
+                *zs_d = zs_in ? tmp.upload(zs_in, n * 32) : nullptr;
+  if (!tmp.ok()) return M3X_ERR_HIP;
   int fail = 1;
-  rc = M3X_ERR_HIP;
-  if (!bl_d || !cs_d || (zs_in && !zs_d)) goto out;
-  if (hipMemsetAsync(w.fail, 0, 4, ctx->stream) != hipSuccess) goto out;
-  if (launch_challenge_eval(ctx, w, bl_d, cs_d, zs_d, n) != M3X_OK) goto out;
-  if (hipMemcpyAsync(out_z, w.zs, n * 32, hipMemcpyDeviceToHost,
-                     ctx->stream) != hipSuccess)
-    goto out;
-  if (hipMemcpyAsync(out_y, w.ys, n * 32, hipMemcpyDeviceToHost,
-                     ctx->stream) != hipSuccess)
-    goto out;
-  if (hipMemcpyAsync(&fail, w.fail, 4, hipMemcpyDeviceToHost, ctx->stream) !=
-      hipSuccess)
-    goto out;
-  if (hipStreamSynchronize(ctx->stream) != hipSuccess) goto out;
-  rc = fail ? M3X_ERR_ENCODING : M3X_OK;
-out:
+  bool queued = hipMemsetAsync(w.fail, 0, 4, ctx->stream) == hipSuccess &&
+                launch_challenge_eval(ctx, w, bl_d, cs_d, zs_d, n) == M3X_OK;
+  if (queued) {
+    tmp.download(out_z, w.zs, n * 32);
+    tmp.download(out_y, w.ys, n * 32);
+    tmp.download(&fail, w.fail, 4);
+  }
+  // on failure too: nothing is freed while stream2 may still read the blobs
   (void)hipStreamSynchronize(ctx->stream2);
-  (void)hipStreamSynchronize(ctx->stream);
-  if (bl_d) (void)hipFree(bl_d);
-  if (cs_d) (void)hipFree(cs_d);
-  if (zs_d) (void)hipFree(zs_d);
-  return rc;
+  if (!tmp.sync() || !queued) return M3X_ERR_HIP;
+  return fail ? M3X_ERR_ENCODING : M3X_OK;
 }
 
 int32_t m3x_kzg_batch_challenge_test(m3x_ctx *ctx, const uint8_t *cs,
@@ -1308,32 +1174,25 @@ int32_t m3x_kzg_batch_challenge_test(m3x_ctx *ctx, const uint8_t *cs,
   KzgWork w;
   int32_t rc = kzg_layout(ctx, n, w);
   if (rc != M3X_OK) return rc;
-  uint8_t *cs_d = dev_copy(cs, n * 48), *pr_d = dev_copy(proofs, n * 48);
+  m3x::DevTemps tmp(ctx->stream);
+  const uint8_t *cs_d = tmp.upload(cs, n * 48),
+                *pr_d = tmp.upload(proofs, n * 48);
+  if (!tmp.ok()) return M3X_ERR_HIP;
   int fail = 1;
-  rc = M3X_ERR_HIP;
-  if (!cs_d || !pr_d) goto out;
-  if (hipMemsetAsync(w.fail, 0, 4, ctx->stream) != hipSuccess) goto out;
-  if (hipMemcpyAsync(w.zs, zs, n * 32, hipMemcpyHostToDevice, ctx->stream) !=
-      hipSuccess)
-    goto out;
-  if (hipMemcpyAsync(w.ys, ys, n * 32, hipMemcpyHostToDevice, ctx->stream) !=
-      hipSuccess)
-    goto out;
-  hipLaunchKernelGGL(k_kzg_batch_r, dim3(1), dim3(256), 0, ctx->stream, cs_d,
-                     pr_d, n, w);
-  if (hipMemcpyAsync(out_r, w.r_out, 32, hipMemcpyDeviceToHost,
-                     ctx->stream) != hipSuccess)
-    goto out;
-  if (hipMemcpyAsync(&fail, w.fail, 4, hipMemcpyDeviceToHost, ctx->stream) !=
-      hipSuccess)
-    goto out;
-  if (hipStreamSynchronize(ctx->stream) != hipSuccess) goto out;
-  rc = fail ? M3X_ERR_ENCODING : M3X_OK;
-out:
-  (void)hipStreamSynchronize(ctx->stream);
-  if (cs_d) (void)hipFree(cs_d);
-  if (pr_d) (void)hipFree(pr_d);
-  return rc;
+  bool queued =
+      hipMemsetAsync(w.fail, 0, 4, ctx->stream) == hipSuccess &&
+      hipMemcpyAsync(w.zs, zs, n * 32, hipMemcpyHostToDevice, ctx->stream) ==
+          hipSuccess &&
+      hipMemcpyAsync(w.ys, ys, n * 32, hipMemcpyHostToDevice, ctx->stream) ==
+          hipSuccess;
+  if (queued) {
+    hipLaunchKernelGGL(k_kzg_batch_r, dim3(1), dim3(256), 0, ctx->stream, cs_d,
+                       pr_d, n, w);
+    tmp.download(out_r, w.r_out, 32);
+    tmp.download(&fail, w.fail, 4);
+  }
+  if (!tmp.sync() || !queued) return M3X_ERR_HIP;
+  return fail ? M3X_ERR_ENCODING : M3X_OK;
 }
 
 } // extern "C"

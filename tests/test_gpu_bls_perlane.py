@@ -11,6 +11,9 @@ inputs and rands. Shapes are the smallest that can break something:
   n = 65   two Miller blocks, ragged last wave; split h2c path (n > 64)
   n = 257  more stage-1 reduce blocks than one, a ragged last one, and
            reduce threads with no element in both stages
+With M3X_LATENCY_MAX=0 as well, the batch also takes the kernels that the
+dispatch otherwise keeps for n > 2^18: the fused k_bls_prepare and the
+default-budget k_bls_h2c_map.
 Set i carries k = 1 + i % 3 public keys and is signed with the sum of the
 member secret keys."""
 import ctypes
@@ -157,6 +160,30 @@ def test_perlane_infinity_signature(ctx, wl):
     inf_sig = bytes([0xC0]) + bytes(95)
     want = wl.want(("inf", 1), 1, sigs=inf_sig)
     with env(M3X_SMALL_MILLER="0"):
+        assert wl.gpu(ctx, 1, sigs=inf_sig) == want
+        assert wl.gpu(ctx, 1) == wl.want(("ok", 1), 1)
+
+
+@pytest.mark.parametrize("n", [3, 65])
+def test_large_batch_regime_valid_tampered_valid(ctx, wl, n):
+    """M3X_LATENCY_MAX=0 sends a small batch through the kernels that
+    otherwise run only above 2^18 sets: the fused k_bls_prepare and the
+    default-budget k_bls_h2c_map. n = 3 has k = 1, 2, 3 and the fused
+    k_bls_h2c; n = 65 has a ragged second wave and the three-pass h2c
+    (k_bls_h2c_expand, k_bls_h2c_map, k_bls_h2c_fin)."""
+    bad = wl.tampered(n)
+    with env(M3X_LATENCY_MAX="0", M3X_SMALL_MILLER="0"):
+        assert wl.gpu(ctx, n) == wl.want(("ok", n), n)
+        assert wl.gpu(ctx, n, msgs=bad) == wl.want(("bad", n), n, msgs=bad)
+        assert wl.gpu(ctx, n) == wl.want(("ok", n), n)
+
+
+def test_large_batch_regime_infinity_signature(ctx, wl):
+    """k_bls_prepare's sig.inf branch: the set contributes an infinite
+    r*sigma and skips the psi subgroup check."""
+    inf_sig = bytes([0xC0]) + bytes(95)
+    want = wl.want(("inf", 1), 1, sigs=inf_sig)
+    with env(M3X_LATENCY_MAX="0", M3X_SMALL_MILLER="0"):
         assert wl.gpu(ctx, 1, sigs=inf_sig) == want
         assert wl.gpu(ctx, 1) == wl.want(("ok", 1), 1)
 

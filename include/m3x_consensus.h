@@ -60,7 +60,8 @@ int32_t m3x_kernel_ms(m3x_ctx *ctx, int32_t kernel_id, double *ms,
 
 /* carry a 32B subtree root from `from_level` to `to_depth` against the
  * zero ladder, then optionally mix_in_length — the multi-GPU cap-finishing
- * primitive paired with m3x_validator_subtree_root_dev. */
+ * primitive paired with m3x_validator_subtree_root_dev. The ladder holds
+ * Z[0..64]: to_depth > 64 is M3X_ERR_ARG. */
 int32_t m3x_finalize_root(m3x_ctx *ctx, const uint8_t node[32],
                           uint32_t from_level, uint32_t to_depth,
                           int64_t mix_len, uint8_t out_root[32]);
@@ -84,7 +85,8 @@ int32_t m3x_merkleize_validators_dev(m3x_ctx *ctx, const void *ssz_dev,
 
 /* merkleize n_chunks 32-byte chunks into a depth-`depth` tree (capacity
  * 2^depth, zero-ladder padded); if mix_len >= 0, mix_in_length(mix_len).
- * Caller zero-pads the tail chunk. */
+ * Caller zero-pads the tail chunk. depth > 64 or n_chunks > 2^depth is
+ * M3X_ERR_ARG. */
 int32_t m3x_merkleize_chunks(m3x_ctx *ctx, const uint8_t *chunks,
                              uint64_t n_chunks, uint32_t depth,
                              int64_t mix_len, uint8_t out_root[32]);
@@ -115,16 +117,20 @@ void m3x_registry_cache_destroy(m3x_registry_cache *cache);
 int32_t m3x_registry_cache_root(m3x_ctx *ctx, m3x_registry_cache *cache,
                                 uint8_t out_root[32]);
 /* apply m updated/appended records at `indices` (each < capacity;
- * n grows to max over indices+1) and return the new root */
+ * n grows to max over indices+1) and return the new root. m > 65536 or an
+ * index >= capacity is M3X_ERR_ARG; a rejected call changes nothing: tree
+ * and length stay as they were. */
 int32_t m3x_registry_cache_update(m3x_ctx *ctx, m3x_registry_cache *cache,
                                   const uint64_t *indices,
                                   const uint8_t *recs /* m*121 */, uint64_t m,
                                   uint8_t out_root[32]);
 
 /* Batched small-container merkleize: element i owns chunks
- * [offsets[i], offsets[i+1]) (<=32 chunks each); out_roots[i] = its
- * hash_tree_root (depth = ceil_log2(count)). One launch for the
- * BeaconState's many tiny containers. */
+ * [offsets[i], offsets[i+1]) (0..32 chunks each); out_roots[i] = its
+ * hash_tree_root (depth = ceil_log2(count); an empty group gives the zero
+ * chunk). One launch for the BeaconState's many tiny containers.
+ * M3X_ERR_ARG, before anything is launched, for n_elems == 0, a group of
+ * more than 32 chunks or offsets that decrease. */
 int32_t m3x_merkleize_batch(m3x_ctx *ctx, const uint8_t *chunks,
                             const uint32_t *offsets, uint64_t n_elems,
                             uint8_t *out_roots);

@@ -270,7 +270,7 @@ int32_t m3x_kernel_ms(m3x_ctx *ctx, int32_t kernel_id, double *ms,
 int32_t m3x_finalize_root(m3x_ctx *ctx, const uint8_t node[32],
                           uint32_t from_level, uint32_t to_depth,
                           int64_t mix_len, uint8_t out_root[32]) {
-  if (!ctx) return M3X_ERR_ARG;
+  if (!ctx || to_depth > 64) return M3X_ERR_ARG; // the ladder ends at Z[64]
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   M3X_HIP_CHECK(hipSetDevice(ctx->device));
   uint8_t *tmp = ctx->small_pool;
@@ -412,8 +412,8 @@ static int32_t reduce_to_root(m3x_ctx *ctx, const uint8_t *nodes_dev,
 int32_t m3x_merkleize_chunks_dev(m3x_ctx *ctx, const void *chunks_dev,
                                  uint64_t n_chunks, uint32_t depth,
                                  int64_t mix_len, uint8_t out_root[32]) {
-  if (!ctx) return M3X_ERR_ARG;
-  if (n_chunks > (1ull << depth) && depth < 63) return M3X_ERR_ARG;
+  if (!ctx || depth > 64) return M3X_ERR_ARG; // the ladder ends at Z[64]
+  if (depth < 63 && n_chunks > (1ull << depth)) return M3X_ERR_ARG;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   M3X_HIP_CHECK(hipSetDevice(ctx->device));
   uint8_t *root_dev = ctx->small_pool + m3x_ctx::SMALL_POOL_IN;
@@ -470,7 +470,8 @@ int32_t m3x_merkleize_chunks(m3x_ctx *ctx, const uint8_t *chunks,
 int32_t m3x_validator_subtree_root_dev(m3x_ctx *ctx, const void *ssz_dev,
                                        uint64_t n, uint32_t depth,
                                        uint8_t out_root[32]) {
-  if (!ctx || (n > (1ull << depth) && depth < 63)) return M3X_ERR_ARG;
+  if (!ctx || depth > 64 || (depth < 63 && n > (1ull << depth)))
+    return M3X_ERR_ARG;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   M3X_HIP_CHECK(hipSetDevice(ctx->device));
   // leaves
@@ -569,6 +570,8 @@ __global__ void k_merkleize_batch(const uint8_t *__restrict__ chunks,
         reinterpret_cast<const uint32_t *>(chunks + 32ull * (c0 + j));
     for (int q = 0; q < 8; q++) node[j][q] = __builtin_bswap32(src[q]);
   }
+  if (cnt == 0) // merkleize([], 0) is the zero chunk
+    for (int q = 0; q < 8; q++) node[0][q] = 0;
   uint32_t depth = 0;
   while ((1u << depth) < cnt) depth++;
   uint32_t m = cnt, level = 0;
@@ -599,7 +602,12 @@ extern "C" int32_t m3x_merkleize_batch(m3x_ctx *ctx, const uint8_t *chunks,
                                        const uint32_t *offsets,
                                        uint64_t n_elems,
                                        uint8_t *out_roots) {
-  if (!ctx || n_elems == 0) return M3X_ERR_ARG;
+  if (!ctx || !offsets || n_elems == 0) return M3X_ERR_ARG;
+  // the kernel folds a group in a private node[32][8]: every count must be
+  // 0..32, so the offsets must not decrease either
+  for (uint64_t i = 0; i < n_elems; i++)
+    if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 32)
+      return M3X_ERR_ARG;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   M3X_HIP_CHECK(hipSetDevice(ctx->device));
   uint64_t in_bytes = (uint64_t)offsets[n_elems] * 32;
@@ -618,8 +626,9 @@ extern "C" int32_t m3x_merkleize_batch(m3x_ctx *ctx, const uint8_t *chunks,
   uint8_t *out_d = base + in_bytes + ((off_bytes + 31) & ~31ull);
   int32_t rc = M3X_OK;
   do {
-    if (hipMemcpyAsync(in_d, chunks, in_bytes, hipMemcpyHostToDevice,
-                       ctx->stream) != hipSuccess ||
+    if ((in_bytes && hipMemcpyAsync(in_d, chunks, in_bytes,
+                                    hipMemcpyHostToDevice,
+                                    ctx->stream) != hipSuccess) ||
         hipMemcpyAsync(off_d, offsets, off_bytes, hipMemcpyHostToDevice,
                        ctx->stream) != hipSuccess) {
       rc = M3X_ERR_HIP;
@@ -870,9 +879,12 @@ int32_t m3x_registry_cache_update(m3x_ctx *ctx, m3x_registry_cache *c,
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   M3X_HIP_CHECK(hipSetDevice(ctx->device));
   if (m) {
+    // validate every index before anything changes: a rejected call leaves
+    // the cache (its length included) as it was
+    uint64_t new_n = c->n;
     for (uint64_t i = 0; i < m; i++) {
       if (indices[i] >= c->capacity) return M3X_ERR_ARG;
-      if (indices[i] + 1 > c->n) c->n = indices[i] + 1;
+      if (indices[i] + 1 > new_n) new_n = indices[i] + 1;
     }
     uint64_t need = m * 121;
     if (c->recs_cap < need) {
@@ -887,6 +899,7 @@ int32_t m3x_registry_cache_update(m3x_ctx *ctx, m3x_registry_cache *c,
                                  hipMemcpyHostToDevice, ctx->stream));
     M3X_HIP_CHECK(hipMemcpyAsync(c->dirty_a, indices, m * 8,
                                  hipMemcpyHostToDevice, ctx->stream));
+    c->n = new_n;
     uint32_t blocks = (uint32_t)((m + 63) / 64);
     hipLaunchKernelGGL(k_cache_update_leaves, dim3(blocks), dim3(64), 0,
                        ctx->stream, c->recs, c->dirty_a, m, c->levels);

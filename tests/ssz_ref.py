@@ -35,6 +35,25 @@ def mix_in_length(root: bytes, length: int) -> bytes:
     return H(root + length.to_bytes(32, "little"))
 
 
+def finalize(node: bytes, from_level: int, to_depth: int, mix_len: int = -1):
+    """carry a subtree root up the left edge of a right-sparse tree: hash it
+    with Z[from_level..to_depth), then mix_in_length unless mix_len < 0"""
+    for level in range(from_level, to_depth):
+        node = H(node + ZEROS[level])
+    return mix_in_length(node, mix_len) if mix_len >= 0 else node
+
+
+def seeded_bytes(tag: bytes, n: int) -> bytes:
+    """n deterministic pseudo-random bytes (SHAKE-256 expansion of tag)"""
+    return hashlib.shake_256(tag).digest(n)
+
+
+def split_chunks(data: bytes, n: int):
+    """the first n 32-byte chunks of data, as a list"""
+    assert len(data) >= 32 * n
+    return [data[32 * i : 32 * i + 32] for i in range(n)]
+
+
 def pack_bytes(data: bytes):
     chunks = []
     for i in range(0, len(data), 32):

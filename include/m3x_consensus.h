@@ -7,6 +7,9 @@
  *  - m3x_bls_verify_sets        <- crypto/bls/src/impls/blst.rs:37-119
  *                                  (bls::verify_signature_sets; the batch
  *                                  equation with host-drawn 64-bit r_i)
+ *  - m3x_bls_verify_each        <- generic_signature_set.rs:111-120
+ *                                  (SignatureSet::verify, once per set: the
+ *                                  gossip drivers' batch-false fallback)
  *  - m3x_bls_pk_decompress      <- blst.rs:130-153 key_validate, as used by
  *                                  validator_pubkey_cache.rs:20-46
  *  - m3x_merkleize_validators   <- BeaconState::update_validators_tree_hash_cache
@@ -53,7 +56,8 @@ int32_t m3x_abi_version(void);
  * 2 finalize, 3 bls_prepare, 4 bls_h2c, 5 bls_miller, 6 bls_reduce,
  * 7 bls_finish, 8 bls_agg, 9 kzg_challenge, 10 kzg_decomp, 11 kzg_eval,
  * 12 kzg_batch_r, 13 kzg_mults, 14 kzg_reduce, 15 kzg_finish,
- * 16 kzgp_quotient, 17 kzgp_msm, 18 kzgp_finish, 19 bls_sigpair). */
+ * 16 kzgp_quotient, 17 kzgp_msm, 18 kzgp_finish, 19 bls_sigpair,
+ * 20 bls_each: the per-set pairing kernel of m3x_bls_verify_each). */
 int32_t m3x_timing_enable(m3x_ctx *ctx, int32_t on);
 int32_t m3x_kernel_ms(m3x_ctx *ctx, int32_t kernel_id, double *ms,
                       uint64_t *launches);
@@ -192,6 +196,27 @@ int32_t m3x_bls_verify_sets_dev(m3x_ctx *ctx, const void *msgs_dev,
                                 const void *sigs_dev, const void *pks_dev,
                                 const void *pk_offsets_dev,
                                 const void *rands_dev, uint64_t n);
+
+/* SignatureSet::verify() for each of n sets, one call: verdicts[i] = 1/0
+ * (generic_signature_set.rs:111-120 -> fast_aggregate_verify,
+ * blst.rs:250-261; what the gossip drivers fall back to when a batch is
+ * false, attestation_verification/batch.rs:109-127 and :195). No
+ * randomiser: verdict_i = 1 iff sigma_i decodes, is in the G2 subgroup
+ * (infinity counts as in), k_i >= 1, every pubkey of the set parses, their
+ * sum apk_i is not infinity and
+ *   final_exp(miller(apk_i, H(m_i)) * miller(-g1, sigma_i)) == 1.
+ * Same input layout as m3x_bls_verify_sets, without rands. Returns M3X_OK
+ * (n == 0 included, nothing written) or a negative error; an invalid set
+ * is verdict 0, never an error, and never changes another set's verdict.
+ * k_i == 0 (pk_offsets[i+1] <= pk_offsets[i]) is verdict 0 for that set. */
+int32_t m3x_bls_verify_each(m3x_ctx *ctx, const uint8_t *msgs,
+                            const uint8_t *sigs, const uint8_t *pks,
+                            const uint32_t *pk_offsets, uint64_t n,
+                            int32_t *verdicts /* n */);
+int32_t m3x_bls_verify_each_dev(m3x_ctx *ctx, const void *msgs_dev,
+                                const void *sigs_dev, const void *pks_dev,
+                                const void *pk_offsets_dev, uint64_t n,
+                                void *verdicts_dev /* n * int32 */);
 
 /* ---- KZG blob proof verification (Deneb; crypto/kzg/src/lib.rs) ----
  *

@@ -215,6 +215,30 @@ def _bind(lib):
             ],
         ),
         (
+            "m3x_bls_verify_each",
+            [
+                ctypes.c_void_p,
+                ctypes.c_char_p,
+                ctypes.c_char_p,
+                ctypes.c_char_p,
+                ctypes.POINTER(ctypes.c_uint32),
+                ctypes.c_uint64,
+                ctypes.POINTER(ctypes.c_int32),
+            ],
+        ),
+        (
+            "m3x_bls_verify_each_dev",
+            [
+                ctypes.c_void_p,
+                ctypes.c_void_p,
+                ctypes.c_void_p,
+                ctypes.c_void_p,
+                ctypes.c_void_p,
+                ctypes.c_uint64,
+                ctypes.c_void_p,
+            ],
+        ),
+        (
             "m3x_kzg_create",
             [ctypes.c_void_p, ctypes.c_char_p,
              ctypes.POINTER(ctypes.c_void_p)],
@@ -399,6 +423,7 @@ class Ctx:
     # stands by tests/test_kzg_prover_ref.py); numbering continues from it
     KERNEL_NAMES_BLS_TAIL = [
         "bls_sigpair",  # signature sum + its Miller loop, on the side stream
+        "bls_each",  # per-set pairing check of m3x_bls_verify_each
     ]
 
     def kernel_times(self):

@@ -238,11 +238,47 @@ def verify_signature_sets_with_fallback(sets, ctx=None):
     sets = list(sets)
     if verify_signature_sets(sets, ctx=ctx):
         return [True] * len(sets)
-    # set.verify() path (generic_signature_set.rs:111-120): single-set
-    # fast_aggregate_verify, no randomizer
-    return [
-        verify_signature_sets([s], ctx=ctx, _rands=[1]) for s in sets
+    # set.verify() for every set, in one GPU call
+    return verify_signature_sets_each(sets, ctx=ctx)
+
+
+def verify_signature_sets_each(sets, ctx=None):
+    """SignatureSet::verify() for every set (generic_signature_set.rs:
+    111-120 -> fast_aggregate_verify, blst.rs:250-261; no randomizer), in
+    one GPU call: a per-set list of bools. The host rules apply per set —
+    an empty signature or an empty key list is False for that set only —
+    and only the remaining sets reach the GPU."""
+    sets = list(sets)
+    out = [False] * len(sets)
+    live = [
+        i for i, s in enumerate(sets)
+        if not s.signature.is_empty() and s.signing_keys
     ]
+    if not live:
+        return out
+    msgs = bytearray()
+    sigs = bytearray()
+    pks = bytearray()
+    offsets = [0]
+    for i in live:
+        s = sets[i]
+        msgs += s.message
+        sigs += s.signature.serialize()
+        for pk in s.signing_keys:
+            pks += pk.serialize_uncompressed()
+        offsets.append(offsets[-1] + len(s.signing_keys))
+    n = len(live)
+    ctx = ctx or _native.default_ctx()
+    off_arr = (ctypes.c_uint32 * (n + 1))(*offsets)
+    verdicts = (ctypes.c_int32 * n)()
+    rc = ctx._lib.m3x_bls_verify_each(
+        ctx.handle, bytes(msgs), bytes(sigs), bytes(pks), off_arr, n, verdicts
+    )
+    if rc != 0:
+        raise Error(f"m3x_bls_verify_each rc={rc}")
+    for i, v in zip(live, verdicts):
+        out[i] = v == 1
+    return out
 
 
 def verify_signature_sets(sets, ctx=None, _rands=None) -> bool:

@@ -56,6 +56,21 @@ struct BlsWork {
   int *verdict;    // [1]
 };
 
+// Where a stage records a malformed input. The batch pipeline has one flag
+// per call: any bad set makes the batch false. The per-set pipeline
+// (m3x_bls_verify_each) marks only the set the input belongs to, so a bad
+// set never changes another set's verdict.
+struct BatchFail {
+  int *flag;
+  __device__ __forceinline__ void mark(uint64_t) const { atomicOr(flag, 1); }
+};
+struct SetFail {
+  int32_t *status; // [n], zeroed per call; non-zero = verdict forced to 0
+  __device__ __forceinline__ void mark(uint64_t set) const {
+    atomicOr(&status[set], 1);
+  }
+};
+
 // ---------------------------------------------------------------- kernels
 
 __global__ __launch_bounds__(64, 1) void k_bls_pk_decompress(const uint8_t *__restrict__ comp,
@@ -96,10 +111,10 @@ constexpr uint32_t kAggMaxBlocks = 32768;
 
 // one WAVE per k>1 set: each lane partial-sums a strided slice of the
 // set's pubkeys in Jacobian form, then an LDS tree reduce (6 levels)
-__global__ __launch_bounds__(64, 1) void k_bls_aggregate_w(
+template <typename Fail>
+__device__ __forceinline__ void aggregate_w_body(
     const uint8_t *__restrict__ pks, const uint32_t *__restrict__ offs,
-    BlsWork w) {
-  __shared__ g1j lds[64];
+    const BlsWork &w, g1j *lds, Fail fail) {
   // grid-stride over the aggregate list: the grid is CAPPED (at
   // kAggMaxBlocks) so a k=1-only workload costs ~nothing — launching n
   // blocks of early-exits measured 183 ms at n=1M (rocprof r02)
@@ -118,12 +133,28 @@ __global__ __launch_bounds__(64, 1) void k_bls_aggregate_w(
     }
     g1j_add_aff(acc, acc, pk);
   }
-  if (bad) atomicOr(w.fail, 1);
+  if (bad) fail.mark(set);
   lds[lane] = acc;
   block_tree_reduce<g1j, 64>(lds, lane, g1j_add_op{});
   if (lane == 0) w.apk[set] = lds[0];
   __syncthreads(); // next grid-stride iteration reuses lds
   }
+}
+
+__global__ __launch_bounds__(64, 1) void k_bls_aggregate_w(
+    const uint8_t *__restrict__ pks, const uint32_t *__restrict__ offs,
+    BlsWork w) {
+  __shared__ g1j lds[64];
+  aggregate_w_body(pks, offs, w, lds, BatchFail{w.fail});
+}
+
+// per-set twin: a pubkey that does not parse marks its own set (the sum of
+// the keys that did parse is still stored, a well-formed point)
+__global__ __launch_bounds__(64, 1) void k_bls_aggregate_w_each(
+    const uint8_t *__restrict__ pks, const uint32_t *__restrict__ offs,
+    BlsWork w, int32_t *__restrict__ status) {
+  __shared__ g1j lds[64];
+  aggregate_w_body(pks, offs, w, lds, SetFail{status});
 }
 
 // FUSED per-set prepare (kept for LARGE batches): at high occupancy the
@@ -491,19 +522,33 @@ __device__ __forceinline__ void sig_aff_load(g2a &sig, const g2j &sj) {
 // sigma (n lanes; the sqrt pow chain dominates), pass 2 is the scalar-mult
 // work in wave-uniform classes. Both take the full register budget (see
 // k_bls_h2c_map_lat).
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
-void k_bls_sigdec_lat(const uint8_t *__restrict__ sigs, uint64_t n,
-                      BlsWork w) {
+template <typename Fail>
+__device__ __forceinline__ void sigdec_lane(const uint8_t *__restrict__ sigs,
+                                            uint64_t n, const BlsWork &w,
+                                            Fail fail) {
   uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   g2a sig;
   if (g2_decompress(sig, sigs + 96 * i) != 0) {
-    atomicOr(w.fail, 1);
+    fail.mark(i);
     sig.inf = 1; // harmless placeholder; the verdict is already forced false
   }
   g2j out;
   g2j_from_aff(out, sig);
   w.sig_aff[i] = out;
+}
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
+void k_bls_sigdec_lat(const uint8_t *__restrict__ sigs, uint64_t n,
+                      BlsWork w) {
+  sigdec_lane(sigs, n, w, BatchFail{w.fail});
+}
+
+// per-set twin: a signature that does not decode marks its own set
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
+void k_bls_sigdec_each(const uint8_t *__restrict__ sigs, uint64_t n,
+                       BlsWork w, int32_t *__restrict__ status) {
+  sigdec_lane(sigs, n, w, SetFail{status});
 }
 
 // THREE-class latency-regime mult pass (3n lanes): A [r]sigma,
@@ -573,6 +618,153 @@ void k_bls_prep_mults3(const uint8_t *__restrict__ pks,
   w.p_scaled[i] = rp;
 }
 
+// ---- per-set pipeline (m3x_bls_verify_each): SignatureSet::verify() for
+// every set, generic_signature_set.rs:111-120 -> fast_aggregate_verify
+// (blst.rs:250-261). Nothing is scaled by a randomiser: n independent
+// equations e(apk_i, H(m_i)) * e(-g1, sigma_i) == 1 have nothing to
+// batch, so classes A and C of k_bls_prep_mults3 have no counterpart.
+
+// pass 2, n lanes: the deferred psi subgroup check (class B above) and the
+// set's aggregate key. apk[i] is the parsed key lifted to Jacobian for
+// k = 1 and k_bls_aggregate_w_each's sum for k > 1; a set without keys, or
+// whose one key does not parse, leaves infinity there.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void k_bls_prep_each(const uint8_t *__restrict__ pks,
+                     const uint32_t *__restrict__ offs, uint64_t n, BlsWork w,
+                     int32_t *__restrict__ status) {
+  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  SetFail fail{status};
+  uint32_t k0 = offs[i], k1 = offs[i + 1];
+  if (k1 <= k0 || k1 - k0 == 1) {
+    g1a pk;
+    if (k1 <= k0 || g1_from_uncomp_trusted(pk, pks + 96 * (uint64_t)k0) != 0)
+      pk.inf = 1; // placeholder
+    g1j apk;
+    g1j_from_aff(apk, pk);
+    w.apk[i] = apk;
+    if (pk.inf) fail.mark(i); // no key, unparsable key or infinity key
+  } else if (g1j_is_inf(w.apk[i])) { // aggregate at infinity -> invalid
+    fail.mark(i);
+  }
+  g2a sig;
+  sig_aff_load(sig, w.sig_aff[i]);
+  if (sig.inf) return; // infinity is a valid element (the equation fails)
+  g2j xsig_j;
+  g2_mul_u64_aff(xsig_j, sig, BLS_X_ABS);
+  if (!psi_eq_neg(sig, xsig_j)) fail.mark(i);
+}
+
+// pass 3, the pairing check, is k_bls_verify_each in m3x_bls_each.hip: a
+// translation unit of its own, so that a second caller of miller_w and
+// final_exp_w here does not change how they inline into the batch tail.
+
+// Above latency_max sets the kernels are issue-bound and the fused,
+// default-register-budget forms win; at or below it the latency-regime
+// forms do. Read per call (as M3X_SMALL_MILLER is) so a small test batch
+// can be sent through the large-batch kernels.
+uint64_t latency_max_sets() {
+  if (const char *e = getenv("M3X_LATENCY_MAX")) return strtoull(e, nullptr, 10);
+  return 1ull << 18;
+}
+
+// collect the k > 1 sets and sum their keys into w.apk; status == nullptr
+// is the batch pipeline (w.fail), else the per-set one
+void launch_aggregate(m3x_ctx *ctx, const void *pks_dev, const void *offs_dev,
+                      uint64_t n, const BlsWork &w, int32_t *status) {
+  uint32_t blocks = (uint32_t)((n + 63) / 64);
+  m3x::time_begin(ctx, M3X_K_BLS_AGG);
+  hipLaunchKernelGGL(k_bls_scan_agg, dim3(blocks), dim3(64), 0, ctx->stream,
+                     (const uint32_t *)offs_dev, n, w);
+  uint32_t agg_blocks = n < kAggMaxBlocks ? (uint32_t)n : kAggMaxBlocks;
+  if (status)
+    hipLaunchKernelGGL(k_bls_aggregate_w_each, dim3(agg_blocks), dim3(64), 0,
+                       ctx->stream, (const uint8_t *)pks_dev,
+                       (const uint32_t *)offs_dev, w, status);
+  else
+    hipLaunchKernelGGL(k_bls_aggregate_w, dim3(agg_blocks), dim3(64), 0,
+                       ctx->stream, (const uint8_t *)pks_dev,
+                       (const uint32_t *)offs_dev, w);
+  m3x::time_end(ctx, M3X_K_BLS_AGG);
+}
+
+// w.h2c[i] = hash_to_curve(msg_i) on the second stream (h2c needs nothing
+// from the prepare kernels, so the two ~1-wave/SIMD chains co-reside), and
+// the main stream's wait for it
+int launch_h2c(m3x_ctx *ctx, const void *msgs_dev, uint64_t n,
+               uint64_t latency_max, const BlsWork &w) {
+  uint32_t blocks = (uint32_t)((n + 63) / 64);
+  m3x::time_begin_s(ctx, M3X_K_BLS_H2C, ctx->stream2);
+  if (n > 64) { // split h2c pays at small n too (per-lane chain is ONE
+                // point + clear, vs two points + clear in the fused form)
+    uint32_t blocks2 = (uint32_t)((2 * n + 63) / 64);
+    hipLaunchKernelGGL(k_bls_h2c_expand, dim3(blocks), dim3(64), 0,
+                       ctx->stream2, (const uint8_t *)msgs_dev, n, w);
+    if (n <= latency_max)
+      hipLaunchKernelGGL(k_bls_h2c_map_lat, dim3(blocks2), dim3(64), 0,
+                         ctx->stream2, n, w);
+    else
+      hipLaunchKernelGGL(k_bls_h2c_map, dim3(blocks2), dim3(64), 0,
+                         ctx->stream2, n, w);
+    hipLaunchKernelGGL(k_bls_h2c_fin, dim3(blocks), dim3(64), 0,
+                       ctx->stream2, n, w);
+  } else {
+    hipLaunchKernelGGL(k_bls_h2c, dim3(blocks), dim3(64), 0, ctx->stream2,
+                       (const uint8_t *)msgs_dev, n, w);
+  }
+  m3x::time_end_s(ctx, M3X_K_BLS_H2C, ctx->stream2);
+  M3X_HIP_CHECK(hipEventRecord(ctx->ev_s2, ctx->stream2));
+  M3X_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->ev_s2, 0));
+  return M3X_OK;
+}
+
+// The per-set pipeline. It shares scratch_a with run_verify under a layout
+// of its own; each call zeroes what it reads before writing (status,
+// agg_count), as run_verify does (fail, agg_count), and both end with the
+// main stream synchronised after it has joined the h2c stream, so neither
+// leaves anything behind for the other. No reductions and no side stream:
+// a verdict belongs to a set.
+int run_each(m3x_ctx *ctx, const void *msgs_dev, const void *sigs_dev,
+             const void *pks_dev, const void *offs_dev, uint64_t n,
+             int32_t *verdicts_dev) {
+  BlsWork w = {};
+  int32_t *status = nullptr;
+  int rc = m3x::carve_scratch(
+      ctx, &ctx->scratch_a, &ctx->scratch_a_bytes, [&](m3x::ScratchCarver &c) {
+        w.apk = c.take<g1j>(n);
+        w.agg_idx = c.take<uint64_t>(n);
+        w.agg_count = c.take<uint32_t>(1);
+        w.h2c = c.take<g2j>(n);
+        w.uni = c.take<uint8_t>(n * 256);
+        w.h2c_pts = c.take<g2j>(2 * n);
+        w.sig_aff = c.take<g2j>(n);
+        status = c.take<int32_t>(n);
+      });
+  if (rc != M3X_OK) return rc;
+  M3X_HIP_CHECK(hipMemsetAsync(status, 0, 4 * n, ctx->stream));
+  M3X_HIP_CHECK(hipMemsetAsync(w.agg_count, 0, 4, ctx->stream));
+  uint32_t blocks = (uint32_t)((n + 63) / 64);
+  launch_aggregate(ctx, pks_dev, offs_dev, n, w, status);
+  m3x::time_begin(ctx, M3X_K_BLS_PREPARE);
+  hipLaunchKernelGGL(k_bls_sigdec_each, dim3(blocks), dim3(64), 0, ctx->stream,
+                     (const uint8_t *)sigs_dev, n, w, status);
+  hipLaunchKernelGGL(k_bls_prep_each, dim3(blocks), dim3(64), 0, ctx->stream,
+                     (const uint8_t *)pks_dev, (const uint32_t *)offs_dev, n,
+                     w, status);
+  m3x::time_end(ctx, M3X_K_BLS_PREPARE);
+  DBG_STEP(ctx, "each prepare");
+  rc = launch_h2c(ctx, msgs_dev, n, latency_max_sets(), w);
+  if (rc != M3X_OK) return rc;
+  DBG_STEP(ctx, "each h2c");
+  m3x::time_begin(ctx, M3X_K_BLS_EACH);
+  m3x::launch_bls_verify_each(ctx->stream, n, w.apk, w.h2c, w.sig_aff, status,
+                              verdicts_dev);
+  m3x::time_end(ctx, M3X_K_BLS_EACH);
+  DBG_STEP(ctx, "each verify");
+  M3X_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return M3X_OK;
+}
+
 int run_verify(m3x_ctx *ctx, const void *msgs_dev, const void *sigs_dev,
                const void *pks_dev, const void *offs_dev,
                const void *rands_dev, uint64_t n, int32_t *out) {
@@ -601,22 +793,8 @@ int run_verify(m3x_ctx *ctx, const void *msgs_dev, const void *sigs_dev,
   M3X_HIP_CHECK(hipMemsetAsync(w.fail, 0, 4, ctx->stream));
   M3X_HIP_CHECK(hipMemsetAsync(w.agg_count, 0, 4, ctx->stream));
   uint32_t blocks = (uint32_t)((n + 63) / 64);
-  m3x::time_begin(ctx, M3X_K_BLS_AGG);
-  hipLaunchKernelGGL(k_bls_scan_agg, dim3(blocks), dim3(64), 0, ctx->stream,
-                     (const uint32_t *)offs_dev, n, w);
-  {
-    uint32_t agg_blocks = n < kAggMaxBlocks ? (uint32_t)n : kAggMaxBlocks;
-    hipLaunchKernelGGL(k_bls_aggregate_w, dim3(agg_blocks), dim3(64), 0,
-                       ctx->stream, (const uint8_t *)pks_dev,
-                       (const uint32_t *)offs_dev, w);
-  }
-  m3x::time_end(ctx, M3X_K_BLS_AGG);
-  // Above latency_max sets the kernels are issue-bound and the fused,
-  // default-register-budget forms win; at or below it the latency-regime
-  // forms do. Read per call (as M3X_SMALL_MILLER is) so a small test batch
-  // can be sent through the large-batch kernels.
-  uint64_t latency_max = 1ull << 18;
-  if (const char *e = getenv("M3X_LATENCY_MAX")) latency_max = strtoull(e, nullptr, 10);
+  launch_aggregate(ctx, pks_dev, offs_dev, n, w, nullptr);
+  uint64_t latency_max = latency_max_sets();
   m3x::time_begin(ctx, M3X_K_BLS_PREPARE);
   if (n > latency_max) {
     // issue-bound regime: the fused shared-chain kernel does less work
@@ -639,27 +817,8 @@ int run_verify(m3x_ctx *ctx, const void *msgs_dev, const void *sigs_dev,
   DBG_STEP(ctx, "prepare");
   // h2c is independent of prepare: run it on the second stream so the two
   // ~1-wave/SIMD kernels co-reside (both fit at 2 waves/SIMD by VGPR count)
-  m3x::time_begin_s(ctx, M3X_K_BLS_H2C, ctx->stream2);
-  if (n > 64) { // split h2c pays at small n too (per-lane chain is ONE
-                // point + clear, vs two points + clear in the fused form)
-    uint32_t blocks2 = (uint32_t)((2 * n + 63) / 64);
-    hipLaunchKernelGGL(k_bls_h2c_expand, dim3(blocks), dim3(64), 0,
-                       ctx->stream2, (const uint8_t *)msgs_dev, n, w);
-    if (n <= latency_max)
-      hipLaunchKernelGGL(k_bls_h2c_map_lat, dim3(blocks2), dim3(64), 0,
-                         ctx->stream2, n, w);
-    else
-      hipLaunchKernelGGL(k_bls_h2c_map, dim3(blocks2), dim3(64), 0,
-                         ctx->stream2, n, w);
-    hipLaunchKernelGGL(k_bls_h2c_fin, dim3(blocks), dim3(64), 0,
-                       ctx->stream2, n, w);
-  } else {
-    hipLaunchKernelGGL(k_bls_h2c, dim3(blocks), dim3(64), 0, ctx->stream2,
-                       (const uint8_t *)msgs_dev, n, w);
-  }
-  m3x::time_end_s(ctx, M3X_K_BLS_H2C, ctx->stream2);
-  M3X_HIP_CHECK(hipEventRecord(ctx->ev_s2, ctx->stream2));
-  M3X_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->ev_s2, 0));
+  rc = launch_h2c(ctx, msgs_dev, n, latency_max, w);
+  if (rc != M3X_OK) return rc;
   DBG_STEP(ctx, "h2c");
   m3x::time_begin(ctx, M3X_K_BLS_MILLER);
   // small batches are latency-bound on the per-lane kernel: go wave-per-set
@@ -849,6 +1008,42 @@ int32_t m3x_bls_verify_sets(m3x_ctx *ctx, const uint8_t *msgs,
   if (!tmp.ok()) return M3X_ERR_HIP;
   return m3x_bls_verify_sets_dev(ctx, msgs_d, sigs_d, pks_d, offs_d, rands_d,
                                  n);
+}
+
+int32_t m3x_bls_verify_each_dev(m3x_ctx *ctx, const void *msgs_dev,
+                                const void *sigs_dev, const void *pks_dev,
+                                const void *pk_offsets_dev, uint64_t n,
+                                void *verdicts_dev) {
+  // one block per set: n is a grid dimension
+  if (!ctx || n > 0x7fffffffull) return M3X_ERR_ARG;
+  if (n == 0) return M3X_OK;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  M3X_HIP_CHECK(hipSetDevice(ctx->device));
+  return run_each(ctx, msgs_dev, sigs_dev, pks_dev, pk_offsets_dev, n,
+                  (int32_t *)verdicts_dev);
+}
+
+int32_t m3x_bls_verify_each(m3x_ctx *ctx, const uint8_t *msgs,
+                            const uint8_t *sigs, const uint8_t *pks,
+                            const uint32_t *pk_offsets, uint64_t n,
+                            int32_t *verdicts) {
+  if (!ctx || n > 0x7fffffffull) return M3X_ERR_ARG;
+  if (n == 0) return M3X_OK;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  M3X_HIP_CHECK(hipSetDevice(ctx->device));
+  uint64_t nk = pk_offsets[n];
+  m3x::DevTemps tmp(ctx->stream);
+  const uint8_t *msgs_d = tmp.upload(msgs, n * 32);
+  const uint8_t *sigs_d = tmp.upload(sigs, n * 96);
+  const uint8_t *pks_d = tmp.upload(pks, nk * 96);
+  const uint32_t *offs_d = tmp.upload(pk_offsets, (n + 1) * 4);
+  int32_t *verdicts_d = tmp.alloc<int32_t>(n * 4);
+  if (!tmp.ok()) return M3X_ERR_HIP;
+  int rc = m3x_bls_verify_each_dev(ctx, msgs_d, sigs_d, pks_d, offs_d, n,
+                                   verdicts_d);
+  if (rc != M3X_OK) return rc;
+  tmp.download(verdicts, verdicts_d, n * 4);
+  return tmp.sync() ? M3X_OK : M3X_ERR_HIP;
 }
 
 } // extern "C"

@@ -26,7 +26,8 @@ enum m3x_kernel_id {
   M3X_K_KZGP_MSM = 17,      // fixed-base MSM: table look-ups + block sums
   M3X_K_KZGP_FINISH = 18,   // last G1 sum + compression
   M3X_K_BLS_SIGPAIR = 19,   // signature sum + its Miller loop (stream3)
-  M3X_K_COUNT = 20
+  M3X_K_BLS_EACH = 20,      // per-set pairing check (m3x_bls_verify_each)
+  M3X_K_COUNT = 21
 };
 
 struct m3x_ctx {
@@ -71,7 +72,19 @@ void time_end_s(m3x_ctx *ctx, int k, hipStream_t st);
     if (_e != hipSuccess) return M3X_ERR_HIP;                                  \
   } while (0)
 
+namespace m3xb {
+struct g1j;
+struct g2j;
+} // namespace m3xb
+
 namespace m3x {
+// m3x_bls_each.hip: the per-set pairing kernel of m3x_bls_verify_each, one
+// wave per set, over the arrays the stages in m3x_bls.hip left behind;
+// verdicts[i] = 1/0, forced to 0 where status[i] != 0
+void launch_bls_verify_each(hipStream_t st, uint64_t n, const m3xb::g1j *apk,
+                            const m3xb::g2j *h2c, const m3xb::g2j *sig_aff,
+                            const int32_t *status, int32_t *verdicts);
+
 // ensure scratch buffer has at least `bytes`; returns 0 or M3X_ERR_*
 int ensure_scratch(m3x_ctx *ctx, uint8_t **buf, uint64_t *cur, uint64_t bytes);
 

@@ -18,6 +18,10 @@
  *  - m3x_merkleize_chunks       <- tree_hash merkle_root + mix_in_length
  *                                  (merkle_proof/src/lib.rs:68-100,
  *                                  deposit_data_tree.rs:26-38)
+ *  - m3x_kzgc_compute_cells,
+ *    m3x_kzgc_verify_cell_proof_batch
+ *                               <- crypto/kzg/src/lib.rs:171-216 (the PeerDAS
+ *                                  cell functions, stubbed TODO(das) there)
  *
  * Conventions: plain pointers + sizes, caller-owned host buffers,
  * synchronous calls (internally pipelined H2D/compute), errors as negative
@@ -57,7 +61,11 @@ int32_t m3x_abi_version(void);
  * 7 bls_finish, 8 bls_agg, 9 kzg_challenge, 10 kzg_decomp, 11 kzg_eval,
  * 12 kzg_batch_r, 13 kzg_mults, 14 kzg_reduce, 15 kzg_finish,
  * 16 kzgp_quotient, 17 kzgp_msm, 18 kzgp_finish, 19 bls_sigpair,
- * 20 bls_each: the per-set pairing kernel of m3x_bls_verify_each). */
+ * 20 bls_each: the per-set pairing kernel of m3x_bls_verify_each,
+ * 21 kzgc_ntt: the three transform passes of m3x_kzgc_compute_cells,
+ * 22 kzgc_decode: canonical check of the cell evaluations, 23 kzgc_combine:
+ * challenge powers, row weights and the per-column interpolation. Cell
+ * verification also counts into 10, 13, 14 and 15, whose work it shares). */
 int32_t m3x_timing_enable(m3x_ctx *ctx, int32_t on);
 int32_t m3x_kernel_ms(m3x_ctx *ctx, int32_t kernel_id, double *ms,
                       uint64_t *launches);
@@ -323,6 +331,68 @@ int32_t m3x_kzg_batch_challenge_test(m3x_ctx *ctx, const uint8_t *cs,
                                      const uint8_t *zs, const uint8_t *ys,
                                      const uint8_t *proofs, uint64_t n,
                                      uint8_t out_r[32]);
+
+/* ---- PeerDAS cell KZG (Fulu; the seam crypto/kzg/src/lib.rs:171-216 stubs
+ * with TODO(das): compute_cells_and_proofs, verify_cell_proof_batch,
+ * cells_to_blob) ----
+ *
+ * A cell is 64 x 32B canonical big-endian scalars (2048 B); a blob extends
+ * to 128 cells. With omega_N = 7^((r-1)/N), cell c holds the blob
+ * polynomial's values on the coset h_c * <omega_64>, h_c =
+ * omega_8192^bitrev7(c), element i at h_c * omega_64^bitrev6(i): the
+ * bit-reversed 8192-point domain, so cells 0..63 are the blob itself
+ * (cells_to_blob, lib.rs:203-206, is their concatenation and needs no call).
+ * Cell proofs are not computed here (lib.rs:171-185 returns both; in Fulu
+ * the proofs arrive with the blob). */
+
+/* The cells of lib.rs:171-185: blobs n*131072 -> cells_out n*128*2048; needs
+ * no setup. M3X_ERR_ENCODING for a non-canonical element; n == 0 is M3X_OK,
+ * nothing written; n > 65535 is M3X_ERR_ARG. */
+int32_t m3x_kzgc_compute_cells(m3x_ctx *ctx, const uint8_t *blobs, uint64_t n,
+                              uint8_t *cells_out);
+int32_t m3x_kzgc_compute_cells_dev(m3x_ctx *ctx, const void *blobs_dev,
+                                  uint64_t n, void *cells_out_dev);
+
+/* The two setup inputs cell verification needs: g1_monomial[0..64) (64*48 B)
+ * and g2_monomial[64] = [tau^64]G2 (96 B). Validated on the device (decodes,
+ * in the subgroup, not infinity; else M3X_ERR_ENCODING and the handle is
+ * unchanged). One load per handle: a second one is M3X_ERR_ARG. */
+int32_t m3x_kzgc_load_cell_setup(m3x_ctx *ctx, m3x_kzg *kzg,
+                                const uint8_t *g1_monomial64,
+                                const uint8_t g2_tau64[96]);
+
+/* Kzg::verify_cell_proof_batch (lib.rs:187-201): n cells, cell k at
+ * (rows[k], cols[k]) of the blob matrix with proof k, against commitment
+ * rows[k] of m. 1 valid / 0 invalid / <0 error; n == 0 returns 1.
+ * M3X_ERR_ARG, before any launch: handle without cell setup, row >= m,
+ * col >= 128, m == 0 with n > 0, n > 65535. M3X_ERR_ENCODING: bad point,
+ * point outside the subgroup, evaluation >= r. The check is
+ *   e(sum r^k pi_k, -[tau^64]G2) *
+ *   e(sum_i w_i C_i - sum_j a_j [tau^j]G1 + sum r^k h_col^64 pi_k, G2) == 1
+ * with w_i the sum of r^k over row i, a_j coefficient j of sum r^k I_k (I_k
+ * the degree < 64 interpolant of cell k), and r = hash_to_bls_field of
+ *   "RCKZGCBATCH__V1_" | BE64(4096) | BE64(64) | BE64(m) | BE64(n) |
+ *   commitments | per cell: BE64(row) BE64(col) cell proof.
+ * There is no _dev form: the transcript is hashed on the calling thread
+ * while the device validates the points, which needs the bytes on the host. */
+int32_t m3x_kzgc_verify_cell_proof_batch(m3x_ctx *ctx, m3x_kzg *kzg,
+                                        const uint8_t *commitments /* m*48 */,
+                                        uint64_t m, const uint64_t *rows,
+                                        const uint64_t *cols /* n each */,
+                                        const uint8_t *cells /* n*2048 */,
+                                        const uint8_t *proofs /* n*48 */,
+                                        uint64_t n);
+
+/* test seam, like m3x_kzg_batch_challenge_test: the challenge r only (host
+ * work; takes no handle). n == 0 or an argument the verify call refuses is
+ * M3X_ERR_ARG. */
+int32_t m3x_kzgc_cell_batch_challenge_test(m3x_ctx *ctx,
+                                          const uint8_t *commitments,
+                                          uint64_t m, const uint64_t *rows,
+                                          const uint64_t *cols,
+                                          const uint8_t *cells,
+                                          const uint8_t *proofs, uint64_t n,
+                                          uint8_t out_r[32]);
 
 #ifdef __cplusplus
 }

@@ -313,6 +313,35 @@ def _bind(lib):
             [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
              ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p],
         ),
+        (
+            "m3x_kzgc_compute_cells",
+            [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64,
+             ctypes.c_char_p],
+        ),
+        (
+            "m3x_kzgc_compute_cells_dev",
+            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+             ctypes.c_void_p],
+        ),
+        (
+            "m3x_kzgc_load_cell_setup",
+            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p,
+             ctypes.c_char_p],
+        ),
+        (
+            "m3x_kzgc_verify_cell_proof_batch",
+            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p,
+             ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+             ctypes.POINTER(ctypes.c_uint64), ctypes.c_char_p,
+             ctypes.c_char_p, ctypes.c_uint64],
+        ),
+        (
+            "m3x_kzgc_cell_batch_challenge_test",
+            [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64,
+             ctypes.POINTER(ctypes.c_uint64),
+             ctypes.POINTER(ctypes.c_uint64), ctypes.c_char_p,
+             ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p],
+        ),
     ]:
         try:
             fn = getattr(lib, name)
@@ -425,10 +454,19 @@ class Ctx:
         "bls_sigpair",  # signature sum + its Miller loop, on the side stream
         "bls_each",  # per-set pairing check of m3x_bls_verify_each
     ]
+    # PeerDAS cell KZG; cell verification also counts into kzg_decomp,
+    # kzg_mults, kzg_reduce and kzg_finish
+    KERNEL_NAMES_KZG_CELLS = [
+        "kzgc_ntt",  # compute_cells: the three transform passes
+        "kzgc_decode",  # cell evaluations: canonical check + decode
+        "kzgc_combine",  # challenge powers, row weights, interpolation
+    ]
 
     def kernel_times(self):
         out = {}
-        for i, name in enumerate(self.KERNEL_NAMES + self.KERNEL_NAMES_BLS_TAIL):
+        names = (self.KERNEL_NAMES + self.KERNEL_NAMES_BLS_TAIL
+                 + self.KERNEL_NAMES_KZG_CELLS)
+        for i, name in enumerate(names):
             ms = ctypes.c_double()
             n = ctypes.c_uint64()
             if self._lib.m3x_kernel_ms(self._h, i, ctypes.byref(ms), ctypes.byref(n)) == 0:

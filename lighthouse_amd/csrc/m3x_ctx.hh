@@ -27,7 +27,10 @@ enum m3x_kernel_id {
   M3X_K_KZGP_FINISH = 18,   // last G1 sum + compression
   M3X_K_BLS_SIGPAIR = 19,   // signature sum + its Miller loop (stream3)
   M3X_K_BLS_EACH = 20,      // per-set pairing check (m3x_bls_verify_each)
-  M3X_K_COUNT = 21
+  M3X_K_KZGC_NTT = 21,      // compute_cells: the three transform passes
+  M3X_K_KZGC_DECODE = 22,   // cell evaluations: canonical check + decode
+  M3X_K_KZGC_COMBINE = 23,  // r powers, row weights, column interpolation
+  M3X_K_COUNT = 24
 };
 
 struct m3x_ctx {

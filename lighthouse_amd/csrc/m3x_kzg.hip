@@ -27,6 +27,7 @@
 #include "bls_device.hh"
 #include "fr_device.hh"
 #include "m3x_ctx.hh"
+#include "m3x_kzg.hh"
 #include "../../include/m3x_consensus.h"
 
 using namespace m3xb;
@@ -35,15 +36,6 @@ using namespace m3xf;
 #define KZG_N 4096
 #define KZG_BLOB_BYTES 131072
 #define KZG_MAX_BATCH 65535 // one grid dimension; far above any block's blobs
-
-// validated setup: device-resident G2 points of the pairing check
-struct m3x_kzg {
-  int device = 0;
-  g2j *g2 = nullptr; // [0] = -[tau]G2, [1] = G2 generator (z = 1)
-  // prover only (m3x_kzgp_load_g1_lagrange): the fixed-base table
-  // T[j][i][d-1] = [d * 2^(4j)] L_i, affine, i in blob (bit-reversed) order
-  struct g1t *table = nullptr;
-};
 
 // affine table entry; no entry is infinity (d * 2^(4j) is never 0 mod r)
 struct g1t {
@@ -65,26 +57,6 @@ struct KzgWork {
   int *fail;       // [1] encoding-error flag
   int *verdict;    // [1]
 };
-
-__device__ __forceinline__ uint32_t ld_be32(const uint8_t *p) {
-  uint32_t v;
-  __builtin_memcpy(&v, p, 4);
-  return __builtin_bswap32(v);
-}
-
-// Jacobian -> 48-byte compressed form, the inverse of g1_decompress: the
-// sign bit follows the same lexicographic rule, infinity is 0xc0 00...
-__device__ inline void g1_compress(uint8_t *out, const g1j &p) {
-  if (g1j_is_inf(p)) {
-    for (int i = 0; i < 48; i++) out[i] = 0;
-    out[0] = 0xC0;
-    return;
-  }
-  g1a a;
-  g1j_to_aff(a, p);
-  fp_to_be48(a.x, out);
-  out[0] |= fp_gt_half(a.y) ? 0xA0 : 0x80;
-}
 
 // "FSBLOBVERIFY_V1_" / "RCKZGBATCH___V1_" as big-endian words / bytes
 __device__ __constant__ static const uint32_t KZG_FS_DOMAIN[4] = {
@@ -342,12 +314,6 @@ __global__ __launch_bounds__(256) void k_kzg_batch_r(
   if (bad) atomicOr(w.fail, 1);
 }
 
-// validate_kzg_g1: decompress (infinity is a valid KZG point, unlike a
-// public key) + subgroup check as in k_bls_pk_decompress
-__device__ inline bool kzg_validate_g1(g1a &p, const uint8_t *src) {
-  return g1_decompress(p, src) == 0 && (p.inf || g1_in_subgroup(p));
-}
-
 // validate_kzg_g1 for every commitment and proof. One lane per point.
 __global__ __launch_bounds__(64, 1) void k_kzg_decomp(
     const uint8_t *__restrict__ cs, const uint8_t *__restrict__ proofs,
@@ -365,21 +331,6 @@ __global__ __launch_bounds__(64, 1) void k_kzg_decomp(
     g1j_from_aff(out, p);
   }
   w.pts[lane] = out;
-}
-
-// [k]B for an affine G1 base, 32-byte big-endian scalar, mixed adds
-__device__ inline void g1_mul_be32_aff(g1j &r, const g1a &base,
-                                       const uint8_t *be) {
-  g1j acc;
-  g1j_set_inf(acc);
-  for (int i = 0; i < 32; i++) {
-    uint8_t byte = be[i];
-    for (int b = 7; b >= 0; b--) {
-      g1j_dbl(acc, acc);
-      if ((byte >> b) & 1) g1j_add_aff(acc, acc, base);
-    }
-  }
-  r = acc;
 }
 
 // the 3n+1 independent scalar multiplications, one lane each, four
@@ -868,6 +819,34 @@ int kzgp_wait(m3x_ctx *ctx, const KzgWork &w) {
 
 } // namespace
 
+// the kernels the cell pipeline reuses (declared in m3x_kzg.hh)
+namespace m3x {
+void launch_kzg_setup(hipStream_t st, const uint8_t *g2_96_dev, g2j *out,
+                      int *fail) {
+  hipLaunchKernelGGL(k_kzg_setup, dim3(1), dim3(1), 0, st, g2_96_dev, out,
+                     fail);
+}
+
+void launch_kzg_sum_g1(hipStream_t st, const g1j *in, uint64_t n, g1j *stage,
+                       g1j *out, const int *fail) {
+  uint32_t blocks = (uint32_t)((n + 255) / 256);
+  if (blocks > 256) blocks = 256;
+  hipLaunchKernelGGL(k_kzg_reduce_g1, dim3(blocks), dim3(256), 0, st, in, n,
+                     stage, fail);
+  hipLaunchKernelGGL(k_kzg_reduce_g1, dim3(1), dim3(256), 0, st, stage,
+                     (uint64_t)blocks, out, fail);
+}
+
+void launch_kzg_finish(hipStream_t st, g1j *sums, int *fail, int *verdict,
+                       const g2j *g2) {
+  KzgWork w{};
+  w.sums = sums;
+  w.fail = fail;
+  w.verdict = verdict;
+  hipLaunchKernelGGL(k_kzg_finish, dim3(1), dim3(64), 0, st, w, g2);
+}
+} // namespace m3x
+
 extern "C" {
 
 int32_t m3x_kzg_create(m3x_ctx *ctx, const uint8_t g2_tau[96],
@@ -898,6 +877,8 @@ void m3x_kzg_destroy(m3x_kzg *kzg) {
   if (hipSetDevice(kzg->device) == hipSuccess) {
     if (kzg->g2) (void)hipFree(kzg->g2);
     if (kzg->table) (void)hipFree(kzg->table);
+    if (kzg->cell_g1) (void)hipFree(kzg->cell_g1);
+    if (kzg->cell_g2) (void)hipFree(kzg->cell_g2);
   }
   delete kzg;
 }

@@ -1,12 +1,16 @@
 """KZG on the GPU — the reference's `Kzg` wrapper
-(crypto/kzg/src/lib.rs:62-167): verify_kzg_proof, verify_blob_kzg_proof and
-verify_blob_kzg_proof_batch, and the producing half blob_to_kzg_commitment,
-compute_kzg_proof and compute_blob_kzg_proof.
+(crypto/kzg/src/lib.rs:62-216): verify_kzg_proof, verify_blob_kzg_proof and
+verify_blob_kzg_proof_batch, the producing half blob_to_kzg_commitment,
+compute_kzg_proof and compute_blob_kzg_proof, and the PeerDAS cell functions
+compute_cells, cells_to_blob and verify_cell_proof_batch (lib.rs:171-216).
 
 Verification needs one trusted-setup point, [tau]G2 (entry 1 of the
 ceremony's g2_monomial list, 96 bytes compressed). Producing commitments
 and proofs also needs the 4096 g1_lagrange points, in the ceremony file's
-order; without them the handle is verification-only. All byte strings are
+order; without them the handle is verification-only. Cell verification
+needs g1_monomial[0..64) and g2_monomial[64] (load_cell_setup, or the
+with_cell_setup constructor); compute_cells needs no setup at all. All
+byte strings are
 the spec's big-endian wire forms. Every verify method returns a bool: a
 proof that does not verify is False; malformed input (bad point encoding, a
 point outside the subgroup, a scalar >= the field modulus, wrong lengths)
@@ -24,9 +28,13 @@ BYTES_PER_BLOB = BYTES_PER_FIELD_ELEMENT * FIELD_ELEMENTS_PER_BLOB
 BYTES_PER_COMMITMENT = 48
 BYTES_PER_PROOF = 48
 BYTES_PER_G2_POINT = 96
+FIELD_ELEMENTS_PER_CELL = 64
+CELLS_PER_EXT_BLOB = 128
+BYTES_PER_CELL = BYTES_PER_FIELD_ELEMENT * FIELD_ELEMENTS_PER_CELL
 BLS_MODULUS = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
 
 _ERR_ENCODING = -4
+_MAX_BATCH = 65535
 
 
 class KzgError(ValueError):
@@ -80,6 +88,7 @@ class Kzg:
                 FIELD_ELEMENTS_PER_BLOB * BYTES_PER_COMMITMENT,
             )
         self._has_basis = False
+        self._has_cell_setup = False
         self._ctx = ctx or _native.default_ctx()
         self._lib = _native.load()
         self._h = ctypes.c_void_p()
@@ -286,8 +295,193 @@ class Kzg:
         )
         self._produced(rc, "compute_blob_kzg_proof_dev")
 
+    # ---- PeerDAS cells (lib.rs:171-216) ----
+    @classmethod
+    def with_cell_setup(cls, g2_tau: bytes, cell_setup, g1_lagrange=None,
+                        ctx: Optional[_native.Ctx] = None):
+        """Kzg(g2_tau, g1_lagrange, ctx) with cell_setup =
+        (g1_monomial[0..64), g2_monomial[64]) loaded."""
+        try:
+            g1_monomial64, g2_tau64 = cell_setup
+        except (TypeError, ValueError):
+            raise KzgError(
+                "cell_setup: expected (g1_monomial[0..64), g2_monomial[64])"
+            ) from None
+        k = cls(g2_tau, g1_lagrange, ctx)
+        try:
+            k.load_cell_setup(g1_monomial64, g2_tau64)
+        except Exception:
+            k.close()
+            raise
+        return k
+
+    def load_cell_setup(self, g1_monomial64, g2_tau64: bytes):
+        """Load g1_monomial[0..64) (64 * 48 bytes, or 64 byte strings) and
+        g2_monomial[64] (96 bytes): what cell verification needs. A refused
+        setup raises KzgError and leaves the handle as it was; one load per
+        handle."""
+        if not isinstance(g1_monomial64, (bytes, bytearray)):
+            if len(g1_monomial64) != FIELD_ELEMENTS_PER_CELL:
+                raise KzgError(
+                    f"cell setup: expected {FIELD_ELEMENTS_PER_CELL} "
+                    f"g1_monomial points, got {len(g1_monomial64)}"
+                )
+            g1_monomial64 = _join("g1_monomial point", g1_monomial64,
+                                  BYTES_PER_COMMITMENT)
+        g1_monomial64 = _check_len(
+            "g1_monomial", g1_monomial64,
+            FIELD_ELEMENTS_PER_CELL * BYTES_PER_COMMITMENT)
+        g2_tau64 = _check_len("g2_tau64", g2_tau64, BYTES_PER_G2_POINT)
+        if self._has_cell_setup:
+            raise KzgError("cell setup already loaded")
+        rc = self._lib.m3x_kzgc_load_cell_setup(
+            self._ctx.handle, self._h, g1_monomial64, g2_tau64)
+        if rc == _ERR_ENCODING:
+            raise KzgError(
+                "cell_setup holds a point that is not a valid non-infinity "
+                "subgroup point"
+            )
+        if rc != 0:
+            raise RuntimeError(f"m3x_kzgc_load_cell_setup failed (rc={rc})")
+        self._has_cell_setup = True
+
+    # ---- lib.rs:171-185, the cells only ----
+    def compute_cells(self, blob: bytes):
+        """The blob's 128 cells of 2048 bytes; cells 0..63 are the blob."""
+        return self.compute_cells_batch([blob])[0]
+
+    def compute_cells_batch(self, blobs: Sequence[bytes]):
+        n = len(blobs)
+        if n == 0:
+            return []
+        if n > _MAX_BATCH:
+            raise KzgError(f"compute_cells: at most {_MAX_BATCH} blobs a call")
+        bl = _join("blob", blobs, BYTES_PER_BLOB)
+        per_blob = CELLS_PER_EXT_BLOB * BYTES_PER_CELL
+        out = ctypes.create_string_buffer(per_blob * n)
+        rc = self._lib.m3x_kzgc_compute_cells(self._ctx.handle, bl, n, out)
+        self._produced(rc, "compute_cells")
+        raw = out.raw
+        return [
+            _split(raw[per_blob * i : per_blob * (i + 1)], BYTES_PER_CELL,
+                   CELLS_PER_EXT_BLOB)
+            for i in range(n)
+        ]
+
+    def compute_cells_batch_dev(self, blobs_dev, n: int, cells_out_dev):
+        """Device-resident form: blobs n*131072 -> cells_out_dev n*262144."""
+        rc = self._lib.m3x_kzgc_compute_cells_dev(
+            self._ctx.handle, blobs_dev, n, cells_out_dev
+        )
+        self._produced(rc, "compute_cells_dev")
+
+    # ---- lib.rs:203-206 ----
+    @staticmethod
+    def cells_to_blob(cells: Sequence[bytes]) -> bytes:
+        """The blob of a full set of 128 cells: cells 0..63 joined (host)."""
+        if len(cells) != CELLS_PER_EXT_BLOB:
+            raise KzgError(
+                f"cells_to_blob: expected {CELLS_PER_EXT_BLOB} cells, "
+                f"got {len(cells)}"
+            )
+        cells = [_check_len("cell", c, BYTES_PER_CELL) for c in cells]
+        return b"".join(cells[: CELLS_PER_EXT_BLOB // 2])
+
+    # ---- lib.rs:187-201 ----
+    def verify_cell_proof_batch(self, cells: Sequence[bytes],
+                                proofs: Sequence[bytes],
+                                coordinates: Sequence[tuple],
+                                commitments: Sequence[bytes]) -> bool:
+        """The reference's shape: cell k sits at coordinates[k] = (row, col)
+        of the blob matrix, row indexing `commitments`."""
+        packed = self._pack_cell_batch(cells, proofs, coordinates, commitments)
+        if packed is None:
+            return True
+        rc = self._lib.m3x_kzgc_verify_cell_proof_batch(
+            self._ctx.handle, self._h, *packed
+        )
+        return _verdict(rc, "verify_cell_proof_batch")
+
+    def verify_cell_kzg_proof_batch(self, commitments_per_cell: Sequence[bytes],
+                                    cell_indices: Sequence[int],
+                                    cells: Sequence[bytes],
+                                    proofs: Sequence[bytes]) -> bool:
+        """The spec's shape: one commitment per cell. Commitments are
+        deduplicated by first appearance into the rows of the form above."""
+        n = len(cells)
+        if not (n == len(commitments_per_cell) == len(cell_indices) == len(proofs)):
+            raise KzgError(
+                "inconsistent array length: "
+                f"{len(commitments_per_cell)} commitments, "
+                f"{len(cell_indices)} cell indices, {n} cells, "
+                f"{len(proofs)} proofs"
+            )
+        row_of, commitments, coordinates = {}, [], []
+        for c, col in zip(commitments_per_cell, cell_indices):
+            c = _check_len("commitment", c, BYTES_PER_COMMITMENT)
+            if c not in row_of:
+                row_of[c] = len(commitments)
+                commitments.append(c)
+            coordinates.append((row_of[c], col))
+        return self.verify_cell_proof_batch(cells, proofs, coordinates, commitments)
+
+    def _pack_cell_batch(self, cells, proofs, coordinates, commitments):
+        """Checked ctypes arguments of a cell batch; None for the empty one."""
+        if not self._has_cell_setup:
+            raise KzgError("verify_cell_proof_batch: this Kzg has no cell "
+                           "setup loaded")
+        return _pack_cell_batch(cells, proofs, coordinates, commitments)
+
+
+def _pack_cell_batch(cells, proofs, coordinates, commitments):
+    n, m = len(cells), len(commitments)
+    if not (n == len(proofs) == len(coordinates)):
+        raise KzgError(
+            "inconsistent array length: "
+            f"{n} cells, {len(proofs)} proofs, {len(coordinates)} coordinates"
+        )
+    cs = _join("commitment", commitments, BYTES_PER_COMMITMENT)
+    ce = _join("cell", cells, BYTES_PER_CELL)
+    ps = _join("proof", proofs, BYTES_PER_PROOF)
+    rows, cols = [], []
+    for coord in coordinates:
+        try:
+            row, col = coord
+            row, col = int(row), int(col)
+        except (TypeError, ValueError):
+            raise KzgError(f"bad coordinate {coord!r}") from None
+        if not 0 <= row < m:
+            raise KzgError(f"row {row} outside the {m} commitments")
+        if not 0 <= col < CELLS_PER_EXT_BLOB:
+            raise KzgError(f"column {col} outside 0..{CELLS_PER_EXT_BLOB - 1}")
+        rows.append(row)
+        cols.append(col)
+    if n == 0:
+        return None
+    if n > _MAX_BATCH:
+        raise KzgError(f"at most {_MAX_BATCH} cells a call")
+    u64n = ctypes.c_uint64 * n
+    return cs, m, u64n(*rows), u64n(*cols), ce, ps, n
+
 
 # ---- test/introspection seams (parity tests; not on the import path) ----
+def cell_batch_challenge(cells: Sequence[bytes], proofs: Sequence[bytes],
+                         coordinates: Sequence[tuple],
+                         commitments: Sequence[bytes],
+                         ctx: Optional[_native.Ctx] = None) -> bytes:
+    """The verify_cell_kzg_proof_batch challenge r, 32 bytes BE."""
+    packed = _pack_cell_batch(cells, proofs, coordinates, commitments)
+    if packed is None:
+        raise KzgError("inconsistent array length")
+    ctx = ctx or _native.default_ctx()
+    out = ctypes.create_string_buffer(32)
+    rc = _native.load().m3x_kzgc_cell_batch_challenge_test(
+        ctx.handle, *packed, out)
+    if rc != 0:
+        raise RuntimeError(f"m3x_kzgc_cell_batch_challenge_test rc={rc}")
+    return out.raw
+
+
 def blob_challenge_eval(blobs: Sequence[bytes], commitments: Sequence[bytes],
                         zs: Optional[Sequence[bytes]] = None,
                         ctx: Optional[_native.Ctx] = None):

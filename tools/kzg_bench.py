@@ -21,7 +21,14 @@ CPU oracle). It first reports the one-time Lagrange load (validation +
 table build), and beside each producing result it prints the kzg_mults
 kernel time of a verification run of the same n in the same process: the
 per-lane 255-step chain the MSM kernels (kzgp_msm + kzgp_finish) are
-measured against."""
+measured against.
+
+--cells times the PeerDAS cell functions, by the same method: compute_cells
+for n = 1 and 6 blobs (device-resident blobs and cells), and
+verify_cell_proof_batch for n = 6 cells (one column of a 6-blob block), 128
+(every column of one blob) and 768 (6 blobs x 128 columns) from host buffers
+(the call has no device-resident form), under the known-tau test setup.
+Inputs, the reference cells and the proofs [q_c(tau)]G1 are prepared once."""
 import argparse
 import ctypes
 import hashlib
@@ -169,6 +176,92 @@ def prove_main(args, fx, triples, ctx, kzg):
     k.close()
 
 
+def cells_main(args, fx, ctx, kzg):
+    import gen_bls_fixtures as G
+    import kzg_cells_ref as C
+    import kzg_ref as K
+
+    cfx = json.loads(
+        (REPO / "tests" / "golden" / "kzg_cell_fixtures.json").read_text())
+    subprocess.run(["make", "-s", "-C", str(REPO / "oracle")], check=True)
+    oracle = ctypes.CDLL(str(REPO / "oracle" / "liboracle.so"))
+    seed = fx["test_setup"]["tau_seed"]
+    tau = int.from_bytes(hashlib.sha256(seed.encode()).digest(), "big") % K.R
+    gen = G.g1_uncompressed(G.G1G)
+
+    def g1_mul(k):
+        k %= K.R
+        if k == 0:
+            return K.G1_POINT_AT_INFINITY
+        out = ctypes.create_string_buffer(96)
+        assert oracle.m3x_oracle_bls_g1_mul(gen, k.to_bytes(32, "big"), out) == 0
+        raw = out.raw
+        return G.g1_compress(
+            (int.from_bytes(raw[:48], "big"), int.from_bytes(raw[48:], "big")))
+
+    mono = b"".join(g1_mul(pow(tau, j, K.R)) for j in range(64))
+    k = kzg.Kzg.with_cell_setup(
+        bytes.fromhex(fx["test_setup"]["g2_tau"]),
+        (mono, bytes.fromhex(cfx["test_setup"]["g2_tau64"])), ctx=ctx)
+    # six distinct blobs: reference cells, commitment, all 128 proofs
+    blobs, ref_cells, commitments, proofs = [], [], [], []
+    for i in range(6):
+        blob = K.blob_from_seed(b"kzg-cells-bench-%d" % i)
+        coef = C.blob_coefficients(blob)
+        blobs.append(blob)
+        ref_cells.append(
+            [C.cell_to_bytes(c) for c in C.cells_from_coefficients(coef)])
+        commitments.append(g1_mul(C.poly_eval(coef, tau)))
+        proofs.append([
+            g1_mul(C.poly_eval(C.cell_quotient(coef, c), tau))
+            for c in range(128)
+        ])
+
+    def report(call, n, unit, times, kernels):
+        med = statistics.median(times)
+        print(json.dumps({
+            "call": call,
+            "n_" + unit: n,
+            "reps": args.reps,
+            "ms_min": round(min(times) * 1e3, 4),
+            "ms_median": round(med * 1e3, 4),
+            "ms_max": round(max(times) * 1e3, 4),
+            unit + "_per_s_median": round(n / med, 2),
+            "kernel_ms_serialised": kernels,
+        }), flush=True)
+
+    for n in (1, 6):
+        blobs_d = ctx.upload(b"".join(blobs[:n]))
+        out_d = ctx.alloc(n * 128 * 2048)
+        run = lambda: k.compute_cells_batch_dev(blobs_d, n, out_d)  # noqa: E731
+        times, kernels = timed(ctx, run, args.reps, args.warmup)
+        got = ctypes.create_string_buffer(n * 128 * 2048)
+        assert ctx._lib.m3x_d2h(ctx.handle, got, out_d, len(got)) == 0
+        assert got.raw == b"".join(b"".join(c) for c in ref_cells[:n]), \
+            "cells differ from the reference"
+        report("compute_cells", n, "blobs", times, kernels)
+        ctx.free(blobs_d)
+        ctx.free(out_d)
+
+    shapes = {
+        6: [(row, 70) for row in range(6)],
+        128: [(0, col) for col in range(128)],
+        768: [(row, col) for col in range(128) for row in range(6)],
+    }
+    for n, coords in shapes.items():
+        cells = [ref_cells[r][c] for r, c in coords]
+        prs = [proofs[r][c] for r, c in coords]
+        m = max(r for r, _ in coords) + 1
+        cs = commitments[:m]
+
+        def run():
+            assert k.verify_cell_proof_batch(cells, prs, coords, cs) is True
+
+        times, kernels = timed(ctx, run, args.reps, args.warmup)
+        report("verify_cell_proof_batch", n, "cells", times, kernels)
+    k.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--sizes", default=None)
@@ -176,6 +269,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--prove", action="store_true",
                     help="time commitment and blob-proof computation instead")
+    ap.add_argument("--cells", action="store_true",
+                    help="time compute_cells and cell-proof batch verification")
     args = ap.parse_args()
     if args.sizes is None:
         args.sizes = "1,6" if args.prove else "1,6,192"
@@ -183,6 +278,8 @@ def main():
     from lighthouse_amd import _native, kzg
 
     fx = json.loads((REPO / "tests" / "golden" / "kzg_fixtures.json").read_text())
+    if args.cells:
+        return cells_main(args, fx, _native.default_ctx(), kzg)
     triples = make_triples(fx["test_setup"]["tau_seed"])
     ctx = _native.default_ctx()
     if args.prove:

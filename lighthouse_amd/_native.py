@@ -5,6 +5,7 @@ missing or fails to load, every call raises. The oracle is never imported
 here (see DESIGN.md §Parity strategy)."""
 import ctypes
 import os
+import threading
 from pathlib import Path
 
 _PKG = Path(__file__).resolve().parent
@@ -483,7 +484,9 @@ class Ctx:
         return out.raw
 
 
-_tls = None
+# created at import: a lazily created one could be installed twice by two
+# racing first calls, orphaning the context the loser had already stored
+_tls = threading.local()
 
 
 def default_ctx() -> Ctx:
@@ -493,11 +496,6 @@ def default_ctx() -> Ctx:
     context — own HIP streams + scratch — so concurrent
     verify_signature_sets calls from different threads run on different
     streams without serializing on one context's lock."""
-    global _tls
-    if _tls is None:
-        import threading
-
-        _tls = threading.local()
     ctx = getattr(_tls, "ctx", None)
     if ctx is None:
         ctx = Ctx(int(os.environ.get("M3X_DEVICE", "0")))

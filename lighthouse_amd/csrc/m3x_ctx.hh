@@ -50,6 +50,11 @@ struct m3x_ctx {
   // persistent pool for small inputs + 32B root slots (avoids per-call
   // hipMalloc/hipFree on the many tiny container merkleizations)
   uint8_t *small_pool = nullptr; // layout: [256 KiB input][64B root]
+  // The root slot at small_pool + SMALL_POOL_IN is [32B result][32B
+  // intermediate], shared by every merkle call that ends in a root copy-back
+  // (chunks, validator subtree / registry, registry cache); pooled inputs and
+  // finalize_root's node stay below SMALL_POOL_IN. All of them hold `mu` and
+  // run on `stream`, so stream order is the only ordering the slot needs.
   static constexpr uint64_t SMALL_POOL_IN = 256 * 1024;
   // per-kernel cumulative time (ms) + launch counts since last reset,
   // measured with hipEvents on `stream`

@@ -87,14 +87,15 @@ int32_t m3x_shuffle_list_dev(m3x_ctx *ctx, void *indices_dev,
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   M3X_HIP_CHECK(hipSetDevice(ctx->device));
   uint64_t n_windows = ((list_size - 1) >> 8) + 1;
-  uint64_t need = 32 + 32 * n_windows + 64;
-  int rc = m3x::ensure_scratch(ctx, &ctx->scratch_b, &ctx->scratch_b_bytes,
-                               need);
+  uint8_t *seed_d = nullptr, *hashes_d = nullptr;
+  uint64_t *pivot_d = nullptr;
+  int rc = m3x::carve_scratch(
+      ctx, &ctx->scratch_b, &ctx->scratch_b_bytes, [&](m3x::ScratchCarver &c) {
+        seed_d = c.take<uint8_t>(32);
+        hashes_d = c.take<uint8_t>(32 * n_windows);
+        pivot_d = c.take<uint64_t>(1);
+      });
   if (rc != M3X_OK) return rc;
-  uint8_t *seed_d = ctx->scratch_b;
-  uint8_t *hashes_d = ctx->scratch_b + 32;
-  uint64_t *pivot_d =
-      reinterpret_cast<uint64_t *>(ctx->scratch_b + 32 + 32 * n_windows);
   M3X_HIP_CHECK(hipMemcpyAsync(seed_d, seed, 32, hipMemcpyHostToDevice,
                                ctx->stream));
   uint32_t hblocks = (uint32_t)((n_windows + 63) / 64);
@@ -125,21 +126,14 @@ int32_t m3x_shuffle_list(m3x_ctx *ctx, uint32_t *indices, uint64_t list_size,
   if (!ctx || list_size == 0 || list_size > (1ull << 24) || rounds == 0)
     return M3X_ERR_ARG;
   M3X_HIP_CHECK(hipSetDevice(ctx->device));
-  void *dev;
-  M3X_HIP_CHECK(hipMalloc(&dev, list_size * 4));
-  if (hipMemcpy(dev, indices, list_size * 4, hipMemcpyHostToDevice) !=
-      hipSuccess) {
-    (void)hipFree(dev);
-    return M3X_ERR_HIP;
-  }
+  m3x::DevTemps tmp(ctx->stream);
+  uint32_t *dev = tmp.upload(indices, list_size * 4);
+  if (!tmp.ok()) return M3X_ERR_HIP;
   int32_t rc = m3x_shuffle_list_dev(ctx, dev, list_size, rounds, seed,
                                     forwards);
-  if (rc == M3X_OK &&
-      hipMemcpy(indices, dev, list_size * 4, hipMemcpyDeviceToHost) !=
-          hipSuccess)
-    rc = M3X_ERR_HIP;
-  (void)hipFree(dev);
-  return rc;
+  if (rc != M3X_OK) return rc;
+  tmp.download(indices, dev, list_size * 4);
+  return tmp.sync() ? M3X_OK : M3X_ERR_HIP;
 }
 
 } // extern "C"

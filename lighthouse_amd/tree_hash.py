@@ -16,26 +16,27 @@ def _ceil_log2(x: int) -> int:
     return d
 
 
+def _root_call(ctx, name: str, *args) -> bytes:
+    """call the C-ABI function `name`(ctx, *args, out_root[32]) on ctx (None =
+    this thread's default) and return the 32-byte root; raises on rc != 0"""
+    ctx = ctx or _native.default_ctx()
+    out = ctypes.create_string_buffer(32)
+    rc = getattr(ctx._lib, name)(ctx.handle, *args, out)
+    if rc != 0:
+        raise RuntimeError(f"{name} rc={rc}")
+    return out.raw
+
+
 def validator_registry_root(ssz: bytes, n: int, ctx=None) -> bytes:
     """hash_tree_root of List[Validator, 2^40] (eth_spec.rs:404) from packed
     121-byte SSZ records."""
-    ctx = ctx or _native.default_ctx()
-    out = ctypes.create_string_buffer(32)
-    rc = ctx._lib.m3x_merkleize_validators(ctx.handle, ssz, n, out)
-    if rc != 0:
-        raise RuntimeError(f"m3x_merkleize_validators rc={rc}")
-    return out.raw
+    return _root_call(ctx, "m3x_merkleize_validators", ssz, n)
 
 
 def merkleize_chunks(chunks: bytes, n_chunks: int, depth: int,
                      mix_len: int = -1, ctx=None) -> bytes:
-    ctx = ctx or _native.default_ctx()
-    out = ctypes.create_string_buffer(32)
-    rc = ctx._lib.m3x_merkleize_chunks(ctx.handle, chunks, n_chunks, depth,
-                                       mix_len, out)
-    if rc != 0:
-        raise RuntimeError(f"m3x_merkleize_chunks rc={rc}")
-    return out.raw
+    return _root_call(ctx, "m3x_merkleize_chunks", chunks, n_chunks, depth,
+                      mix_len)
 
 
 def basic_list_root(data: bytes, n_elems: int, elem_size: int,
@@ -60,15 +61,8 @@ def basic_vector_root(data: bytes, n_elems: int, elem_size: int, ctx=None) -> by
 def merkleize_chunks_dev(dev_ptr, n_chunks: int, depth: int, mix_len: int = -1,
                          ctx=None) -> bytes:
     """device-resident chunk buffer (zero-padded tail chunk)."""
-    import ctypes as ct
-
-    ctx = ctx or _native.default_ctx()
-    out = ct.create_string_buffer(32)
-    rc = ctx._lib.m3x_merkleize_chunks_dev(ctx.handle, dev_ptr, n_chunks,
-                                           depth, mix_len, out)
-    if rc != 0:
-        raise RuntimeError(f"m3x_merkleize_chunks_dev rc={rc}")
-    return out.raw
+    return _root_call(ctx, "m3x_merkleize_chunks_dev", dev_ptr, n_chunks,
+                      depth, mix_len)
 
 
 def basic_list_root_dev(dev_ptr, n_elems: int, elem_size: int,
@@ -91,14 +85,7 @@ def root_vector_root_dev(dev_ptr, n: int, ctx=None) -> bytes:
 
 
 def validator_registry_root_dev(dev_ptr, n: int, ctx=None) -> bytes:
-    import ctypes as ct
-
-    ctx = ctx or _native.default_ctx()
-    out = ct.create_string_buffer(32)
-    rc = ctx._lib.m3x_merkleize_validators_dev(ctx.handle, dev_ptr, n, out)
-    if rc != 0:
-        raise RuntimeError(f"m3x_merkleize_validators_dev rc={rc}")
-    return out.raw
+    return _root_call(ctx, "m3x_merkleize_validators_dev", dev_ptr, n)
 
 
 def root_vector_root(roots: bytes, n: int, ctx=None) -> bytes:
@@ -113,8 +100,6 @@ def merkleize_batch(chunk_groups, ctx=None):
     """One GPU launch for many tiny containers: chunk_groups is a list of
     bytes (each a concatenation of 32B chunks, <=32 chunks per group);
     returns the list of hash_tree_roots (depth = ceil_log2(count))."""
-    import ctypes as ct
-
     ctx = ctx or _native.default_ctx()
     offsets = [0]
     blob = bytearray()
@@ -123,8 +108,8 @@ def merkleize_batch(chunk_groups, ctx=None):
         blob += g
         offsets.append(offsets[-1] + len(g) // 32)
     n = len(chunk_groups)
-    off = (ct.c_uint32 * (n + 1))(*offsets)
-    out = ct.create_string_buffer(32 * n)
+    off = (ctypes.c_uint32 * (n + 1))(*offsets)
+    out = ctypes.create_string_buffer(32 * n)
     rc = ctx._lib.m3x_merkleize_batch(ctx.handle, bytes(blob), off, n, out)
     if rc != 0:
         raise RuntimeError(f"m3x_merkleize_batch rc={rc}")
@@ -137,12 +122,10 @@ class RegistryCache:
     lives in HBM; updates rehash only dirty leaves + root paths."""
 
     def __init__(self, ssz: bytes, n: int, ctx=None):
-        import ctypes as ct
-
         self._ctx = ctx or _native.default_ctx()
-        self._h = ct.c_void_p()
+        self._h = ctypes.c_void_p()
         rc = self._ctx._lib.m3x_registry_cache_create(
-            self._ctx.handle, ssz, n, ct.byref(self._h)
+            self._ctx.handle, ssz, n, ctypes.byref(self._h)
         )
         if rc != 0:
             raise RuntimeError(f"m3x_registry_cache_create rc={rc}")
@@ -159,28 +142,13 @@ class RegistryCache:
             pass
 
     def root(self) -> bytes:
-        import ctypes as ct
-
-        out = ct.create_string_buffer(32)
-        rc = self._ctx._lib.m3x_registry_cache_root(
-            self._ctx.handle, self._h, out
-        )
-        if rc != 0:
-            raise RuntimeError(f"m3x_registry_cache_root rc={rc}")
-        return out.raw
+        return _root_call(self._ctx, "m3x_registry_cache_root", self._h)
 
     def update(self, indices, records: bytes) -> bytes:
         """apply updated/appended 121B records at `indices`; returns the
         new List[Validator, 2^40] root."""
-        import ctypes as ct
-
         m = len(indices)
         assert len(records) == 121 * m
-        idx = (ct.c_uint64 * max(m, 1))(*indices)
-        out = ct.create_string_buffer(32)
-        rc = self._ctx._lib.m3x_registry_cache_update(
-            self._ctx.handle, self._h, idx, records, m, out
-        )
-        if rc != 0:
-            raise RuntimeError(f"m3x_registry_cache_update rc={rc}")
-        return out.raw
+        idx = (ctypes.c_uint64 * max(m, 1))(*indices)
+        return _root_call(self._ctx, "m3x_registry_cache_update", self._h,
+                          idx, records, m)

@@ -43,3 +43,13 @@ def test_library_exports_all():
     for sym in EXPECTED:
         assert hasattr(lib, sym), f"missing export {sym}"
     assert lib.m3x_abi_version() >= 1
+
+
+def test_default_ctx_slot_exists_at_import():
+    """the per-thread slot of default_ctx() is made at import, not by the
+    first call: two first calls racing could each install their own"""
+    import threading
+
+    import lighthouse_amd._native as native
+
+    assert isinstance(native._tls, threading.local)

@@ -2,8 +2,10 @@
 hashlib restatement (ssz_ref): the 9-level passes of k_reduce, the pooled /
 allocated input switch, the high word of the mixed-in length, the sharded
 registry root (subtree roots + finalize_root), the batched small-container
-kernel over every group size, and the registry cache at its capacity edges
-and error returns."""
+kernel over every group size, the registry cache at its capacity edges and
+error returns, the registry root's host and device forms at the leaf-block
+edges, the shared root slot under interleaved calls, and a refused context
+create."""
 import ctypes
 import random
 
@@ -13,6 +15,7 @@ import ssz_ref
 
 pytestmark = pytest.mark.gpu
 
+M3X_ERR_HIP = -1
 M3X_ERR_ARG = -2
 BIG_N = 262145  # first chunk count that needs three k_reduce passes
 
@@ -425,3 +428,76 @@ def test_cache_error_returns(ctx, recs):
                                        ctypes.byref(h))
     assert rc == M3X_ERR_ARG
     assert not h
+
+
+# ------------------------------- 5. registry root forms, root slot, contexts
+
+@pytest.mark.parametrize("n", [0, 1, 3, 256, 257])
+def test_registry_root_host_and_dev(ctx, registry, n):
+    """n = 0 is the ladder entry plus the length mix, 1 a single leaf with no
+    reduce pass, 256 the exact leaf block, 257 a second block; 121 * 3 and
+    121 * 257 are ragged modulo 4"""
+    from lighthouse_amd import tree_hash as th
+
+    ssz, root_of = registry
+    want = root_of(n)
+    if n == 0:
+        assert want == ssz_ref.mix_in_length(ssz_ref.ZEROS[40], 0)
+    assert th.validator_registry_root(ssz[: 121 * n], n, ctx=ctx) == want
+    p = ctx.upload(ssz[: 121 * n] + b"\x00" * 4)
+    try:
+        dev = th.validator_registry_root_dev(p, n, ctx=ctx)
+    finally:
+        ctx.free(p)
+    assert dev == want
+
+
+def test_root_slot_interleaving(ctx, blob, registry, recs):
+    """every call that ends in the context's root slot or its pooled input,
+    back to back on one context in both orders: none may see another's
+    leftovers"""
+    from lighthouse_amd import tree_hash as th
+
+    ssz, root_of = registry
+    node = ssz_ref.seeded_bytes(b"interleave-node", 32)
+    groups = cut_groups(blob, [3, 0, 32, 17])
+    n_cache = 257
+
+    def cache_root():
+        cache, _ = make_cache(ctx, recs, n_cache)
+        try:
+            return cache.root()
+        finally:
+            cache.close()
+
+    p = ctx.upload(ssz[: 121 * 257] + b"\x00" * 4)
+    steps = [
+        # 8192 chunks fill the whole pooled input
+        ("chunks", lambda: th.merkleize_chunks(blob[: 32 * 8192], 8192, 13, ctx=ctx),
+         ssz_ref.merkleize(ssz_ref.split_chunks(blob, 8192), 13)),
+        ("registry_dev", lambda: th.validator_registry_root_dev(p, 257, ctx=ctx),
+         root_of(257)),
+        ("finalize", lambda: ctx.finalize_root(node, 20, 40, 5),
+         ssz_ref.finalize(node, 20, 40, 5)),
+        ("batch", lambda: th.merkleize_batch(groups, ctx=ctx), batch_want(groups)),
+        ("cache", cache_root,
+         model_root([ssz_ref.validator_leaf(r) for r in recs[:n_cache]])),
+    ]
+    try:
+        for name, call, want in steps + steps[::-1]:
+            assert call() == want, name
+    finally:
+        ctx.free(p)
+
+
+def test_ctx_create_invalid_device(ctx, blob):
+    """an ordinal the runtime rejects on the host: the half-built context is
+    torn down, the out pointer stays null, other contexts are unaffected"""
+    import torch
+
+    h = ctypes.c_void_p()
+    rc = ctx._lib.m3x_ctx_create(ctypes.byref(h), torch.cuda.device_count())
+    assert rc == M3X_ERR_HIP
+    assert not h
+    host, dev = both_forms(ctx, blob, 8, 3, -1)
+    assert host == dev == ssz_ref.merkleize(ssz_ref.split_chunks(blob, 8), 3)

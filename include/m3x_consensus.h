@@ -19,7 +19,8 @@
  *                                  (merkle_proof/src/lib.rs:68-100,
  *                                  deposit_data_tree.rs:26-38)
  *  - m3x_kzgc_compute_cells,
- *    m3x_kzgc_verify_cell_proof_batch
+ *    m3x_kzgc_verify_cell_proof_batch,
+ *    m3x_kzgc_recover_cells
  *                               <- crypto/kzg/src/lib.rs:171-216 (the PeerDAS
  *                                  cell functions, stubbed TODO(das) there)
  *
@@ -64,8 +65,10 @@ int32_t m3x_abi_version(void);
  * 20 bls_each: the per-set pairing kernel of m3x_bls_verify_each,
  * 21 kzgc_ntt: the three transform passes of m3x_kzgc_compute_cells,
  * 22 kzgc_decode: canonical check of the cell evaluations, 23 kzgc_combine:
- * challenge powers, row weights and the per-column interpolation. Cell
- * verification also counts into 10, 13, 14 and 15, whose work it shares). */
+ * challenge powers, row weights and the per-column interpolation,
+ * 24 kzgc_recover: the vanishing values and the five transform passes of
+ * m3x_kzgc_recover_cells. Cell verification also counts into 10, 13, 14 and
+ * 15, whose work it shares). */
 int32_t m3x_timing_enable(m3x_ctx *ctx, int32_t on);
 int32_t m3x_kernel_ms(m3x_ctx *ctx, int32_t kernel_id, double *ms,
                       uint64_t *launches);
@@ -334,7 +337,7 @@ int32_t m3x_kzg_batch_challenge_test(m3x_ctx *ctx, const uint8_t *cs,
 
 /* ---- PeerDAS cell KZG (Fulu; the seam crypto/kzg/src/lib.rs:171-216 stubs
  * with TODO(das): compute_cells_and_proofs, verify_cell_proof_batch,
- * cells_to_blob) ----
+ * cells_to_blob, recover_all_cells) ----
  *
  * A cell is 64 x 32B canonical big-endian scalars (2048 B); a blob extends
  * to 128 cells. With omega_N = 7^((r-1)/N), cell c holds the blob
@@ -393,6 +396,30 @@ int32_t m3x_kzgc_cell_batch_challenge_test(m3x_ctx *ctx,
                                           const uint8_t *cells,
                                           const uint8_t *proofs, uint64_t n,
                                           uint8_t out_r[32]);
+
+/* Kzg::recover_all_cells (lib.rs:208-216), for n blobs that share one set of
+ * known columns (a reconstructing node holds whole data columns): from k >= 64
+ * of a blob's 128 cells, all 128. Blob b's known cell t is at
+ * cells + (b*k + t)*2048 and is cell number cell_ids[t]; the ids may come in
+ * any order, the output is always cells 0..127 in order. Needs no setup and
+ * no m3x_kzg handle, like m3x_kzgc_compute_cells.
+ * M3X_ERR_ARG, before any launch: k < 64, k > 128, an id >= 128, a repeated
+ * id, n > 65535. n == 0 is M3X_OK and nothing is written (the argument checks
+ * still apply). M3X_ERR_ENCODING: an evaluation >= r, or known cells that do
+ * not lie on one polynomial of degree < 4096 (possible only when k > 64; the
+ * check is exact: the recovered quotient's coefficients 4096..8191 must all
+ * be zero, and then it agrees with every known cell). On an error the output
+ * buffer's contents are unspecified; the context stays usable.
+ * Method: the spec's recover_polynomialcoeff, the vanishing polynomial of the
+ * missing cells taken by its 128 values per domain instead of being formed;
+ * three 8192-point transforms and the forward half of compute_cells. Cell
+ * proofs are not recomputed. */
+int32_t m3x_kzgc_recover_cells(m3x_ctx *ctx, const uint64_t *cell_ids, uint64_t k,
+                               const uint8_t *cells /* n*k*2048, blob-major */,
+                               uint64_t n, uint8_t *cells_out /* n*128*2048 */);
+int32_t m3x_kzgc_recover_cells_dev(m3x_ctx *ctx, const uint64_t *cell_ids /* host */,
+                                   uint64_t k, const void *cells_dev, uint64_t n,
+                                   void *cells_out_dev);
 
 #ifdef __cplusplus
 }

@@ -343,6 +343,18 @@ def _bind(lib):
              ctypes.POINTER(ctypes.c_uint64), ctypes.c_char_p,
              ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p],
         ),
+        (
+            "m3x_kzgc_recover_cells",
+            [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
+             ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64,
+             ctypes.c_char_p],
+        ),
+        (
+            "m3x_kzgc_recover_cells_dev",
+            [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
+             ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+             ctypes.c_void_p],
+        ),
     ]:
         try:
             fn = getattr(lib, name)
@@ -462,11 +474,15 @@ class Ctx:
         "kzgc_decode",  # cell evaluations: canonical check + decode
         "kzgc_combine",  # challenge powers, row weights, interpolation
     ]
+    # a list of its own: tests/test_kzg_cells_ref.py pins the one above
+    KERNEL_NAMES_KZG_RECOVER = [
+        "kzgc_recover",  # recover_cells: vanishing values + five passes
+    ]
 
     def kernel_times(self):
         out = {}
         names = (self.KERNEL_NAMES + self.KERNEL_NAMES_BLS_TAIL
-                 + self.KERNEL_NAMES_KZG_CELLS)
+                 + self.KERNEL_NAMES_KZG_CELLS + self.KERNEL_NAMES_KZG_RECOVER)
         for i, name in enumerate(names):
             ms = ctypes.c_double()
             n = ctypes.c_uint64()

@@ -30,7 +30,8 @@ enum m3x_kernel_id {
   M3X_K_KZGC_NTT = 21,      // compute_cells: the three transform passes
   M3X_K_KZGC_DECODE = 22,   // cell evaluations: canonical check + decode
   M3X_K_KZGC_COMBINE = 23,  // r powers, row weights, column interpolation
-  M3X_K_COUNT = 24
+  M3X_K_KZGC_RECOVER = 24,  // recover_cells: vanishing values + five passes
+  M3X_K_COUNT = 25
 };
 
 struct m3x_ctx {

@@ -11,10 +11,10 @@
 // omega_8192^bitrev7(c), element i at h_c * omega_64^bitrev6(i). Cells 0..63
 // are the blob itself.
 //
-// fr_ntt64_wave is the core: a 64-point radix-2 transform over Fr, one
-// element per lane, the six butterfly stages exchanged with __shfl_xor (no
-// LDS). Decimation in time takes bit-reversed input to natural output,
-// decimation in frequency the other way round, so no kernel permutes.
+// fr_ntt64_wave (kzg_ntt.hh, shared with cell recovery) is the core: a
+// 64-point radix-2 transform over Fr, one element per lane, the six butterfly
+// stages exchanged with __shfl_xor (no LDS). The row and column steps of the
+// four-step transforms come from the same header.
 //
 // compute_cells: each 4096-point transform is a 64 x 64 four-step
 // decomposition over that core, one wave per row or column, staged through
@@ -43,6 +43,7 @@
 #include "bls_device.hh"
 #include "fr_device.hh"
 #include "kzg_cell_consts.h"
+#include "kzg_ntt.hh"
 #include "m3x_ctx.hh"
 #include "m3x_kzg.hh"
 #include "../../include/m3x_consensus.h"
@@ -50,7 +51,6 @@
 using namespace m3xb;
 using namespace m3xf;
 
-#define KZG_N 4096
 #define KZG_BLOB_BYTES 131072
 #define KZGC_CELL 64                                  // field elements
 #define KZGC_CELLS 128                                // per extended blob
@@ -60,72 +60,7 @@ using namespace m3xf;
 
 namespace {
 
-#define FRC_LOAD(dst, C)                                                       \
-  do {                                                                         \
-    _Pragma("unroll") for (int _i = 0; _i < 8; _i++)(dst).v[_i] = C[_i];       \
-  } while (0)
-
-__device__ __forceinline__ uint32_t bitrev_lo(uint32_t v, int bits) {
-  return __builtin_bitreverse32(v) >> (32 - bits);
-}
-
-__device__ __forceinline__ void fr_pow_u32(fr &r, const fr &a, uint32_t e) {
-  fr_pow(r, a, &e, 1);
-}
-
-// every lane's partner value, lane ^ mask
-__device__ __forceinline__ void fr_shfl_xor(fr &r, const fr &a, int mask) {
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.v[i] = (uint32_t)__shfl_xor((int)a.v[i], mask, 64);
-}
-
-__device__ __forceinline__ void fr_select(fr &r, bool c, const fr &a,
-                                          const fr &b) {
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.v[i] = c ? a.v[i] : b.v[i];
-}
-
-// 64-point transform across one full wave, lane l holding one element:
-//   X[k] = sum_j x[j] * w^(jk),  w = omega_64 (INV: omega_64^-1, unscaled)
-// DIF = false: lane l holds x[bitrev6(l)] on entry and X[l] on return
-// DIF = true:  lane l holds x[l] on entry and X[bitrev6(l)] on return
-// All 64 lanes must be active. Every lane multiplies and the result is
-// selected: a branch would run both sides for the wave anyway.
-template <bool DIF, bool INV>
-__device__ __forceinline__ void fr_ntt64_wave(fr &a, int lane) {
-#pragma unroll
-  for (int s = 0; s < 6; s++) {
-    const int half = DIF ? (32 >> s) : (1 << s);
-    const bool hi = (lane & half) != 0;
-    uint32_t e = (uint32_t)(lane & (half - 1)) * (uint32_t)(32 / half);
-    if (INV) e = (64 - e) & 63;
-    fr tw, t, p, sum, dif;
-    FRC_LOAD(tw, FRC_W64_MONT[e]);
-    t = a;
-    if (!DIF && half > 1) { // the upper input is twiddled before the butterfly
-      fr m;
-      fr_mul(m, a, tw);
-      fr_select(t, hi, m, a);
-    }
-    fr_shfl_xor(p, t, half);
-    fr_add(sum, t, p);
-    fr_sub(dif, p, t);
-    if (DIF && half > 1) fr_mul(dif, dif, tw); // ... or the lower output after
-    fr_select(a, hi, dif, sum);
-  }
-}
-
-__device__ __forceinline__ void st_be32(uint8_t *p, uint32_t v) {
-  v = __builtin_bswap32(v);
-  __builtin_memcpy(p, &v, 4);
-}
-
 // ----------------------------------------------------------- compute_cells
-
-// The wave a thread belongs to, out of 4 per block, and its lane
-__device__ __forceinline__ uint64_t wave_index() {
-  return (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-}
 
 // Inverse transform, rows. With n = 64 n1 + n2 the natural-order index of an
 // evaluation, blob element 64 c + l is e[64 bitrev6(l) + bitrev6(c)]: wave
@@ -153,12 +88,9 @@ __global__ __launch_bounds__(256) void k_kzgc_rows(
 #pragma unroll
     for (int i = 0; i < 8; i++) s[i] = 0;
   }
-  fr a, w, tw;
+  fr a, w;
   fr_from_std(a, s);
-  fr_ntt64_wave<false, true>(a, (int)l);
-  FRC_LOAD(w, FRC_OMEGA4096_INV_MONT);
-  fr_pow_u32(tw, w, bitrev_lo(c, 6) * l);
-  fr_mul(a, a, tw);
+  kzgc_inv_row(a, c, l);
   FRC_LOAD(w, FR_N_INV_MONT);
   fr_mul(a, a, w);
   t1[b * KZG_N + l * 64 + c] = a;
@@ -176,15 +108,9 @@ __global__ __launch_bounds__(256) void k_kzgc_mid(const fr *__restrict__ t1,
   uint64_t b = wv >> 6;
   uint32_t k1 = (uint32_t)wv & 63, l = threadIdx.x & 63;
   if (b >= n) return; // wave-uniform
-  fr a = t1[b * KZG_N + k1 * 64 + l], w, tw;
+  fr a = t1[b * KZG_N + k1 * 64 + l];
   fr_ntt64_wave<false, true>(a, (int)l);
-  FRC_LOAD(w, FRC_OMEGA8192_MONT);
-  fr_pow_u32(tw, w, k1 + 64 * l);
-  fr_mul(a, a, tw);
-  fr_ntt64_wave<true, false>(a, (int)l);
-  FRC_LOAD(w, FR_OMEGA_MONT);
-  fr_pow_u32(tw, w, k1 * bitrev_lo(l, 6));
-  fr_mul(a, a, tw);
+  kzgc_fwd_row<true>(a, k1, l);
   t2[b * KZG_N + l * 64 + k1] = a;
 }
 
@@ -199,12 +125,8 @@ __global__ __launch_bounds__(256) void k_kzgc_cols(const fr *__restrict__ t2,
   uint32_t c = (uint32_t)wv & 63, l = threadIdx.x & 63;
   if (b >= n) return; // wave-uniform
   fr a = t2[b * KZG_N + c * 64 + l];
-  fr_ntt64_wave<true, false>(a, (int)l);
-  uint32_t s[8];
-  fr_to_std(s, a);
-  uint8_t *dst = cells + b * KZGC_EXT_BYTES + (64 * (64 + c) + l) * 32;
-#pragma unroll
-  for (int i = 0; i < 8; i++) st_be32(dst + 4 * i, s[7 - i]);
+  kzgc_fwd_col_store(
+      a, l, cells + b * KZGC_EXT_BYTES + (64 * (64 + c) + l) * 32);
 }
 
 struct CellsWork {

@@ -2,16 +2,16 @@
 (crypto/kzg/src/lib.rs:62-216): verify_kzg_proof, verify_blob_kzg_proof and
 verify_blob_kzg_proof_batch, the producing half blob_to_kzg_commitment,
 compute_kzg_proof and compute_blob_kzg_proof, and the PeerDAS cell functions
-compute_cells, cells_to_blob and verify_cell_proof_batch (lib.rs:171-216).
+compute_cells, cells_to_blob, verify_cell_proof_batch and recover_all_cells
+(lib.rs:171-216).
 
 Verification needs one trusted-setup point, [tau]G2 (entry 1 of the
 ceremony's g2_monomial list, 96 bytes compressed). Producing commitments
 and proofs also needs the 4096 g1_lagrange points, in the ceremony file's
 order; without them the handle is verification-only. Cell verification
 needs g1_monomial[0..64) and g2_monomial[64] (load_cell_setup, or the
-with_cell_setup constructor); compute_cells needs no setup at all. All
-byte strings are
-the spec's big-endian wire forms. Every verify method returns a bool: a
+with_cell_setup constructor); compute_cells and recover_all_cells need no
+setup at all. All byte strings are the spec's big-endian wire forms. Every verify method returns a bool: a
 proof that does not verify is False; malformed input (bad point encoding, a
 point outside the subgroup, a scalar >= the field modulus, wrong lengths)
 or a producing call without the Lagrange basis raises KzgError, the
@@ -33,6 +33,7 @@ CELLS_PER_EXT_BLOB = 128
 BYTES_PER_CELL = BYTES_PER_FIELD_ELEMENT * FIELD_ELEMENTS_PER_CELL
 BLS_MODULUS = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
 
+_ERR_ARG = -2
 _ERR_ENCODING = -4
 _MAX_BATCH = 65535
 
@@ -387,6 +388,65 @@ class Kzg:
         cells = [_check_len("cell", c, BYTES_PER_CELL) for c in cells]
         return b"".join(cells[: CELLS_PER_EXT_BLOB // 2])
 
+    # ---- lib.rs:208-216 ----
+    def recover_all_cells(self, cell_ids: Sequence[int],
+                          cells: Sequence[bytes]):
+        """All 128 cells of a blob from at least 64 of them: cells[t] is
+        cell number cell_ids[t], in any order. KzgError for fewer than 64 or
+        more than 128 cells, an id outside 0..127 or given twice, a
+        non-canonical element, or cells that lie on no blob polynomial."""
+        return self.recover_all_cells_batch(cell_ids, [cells])[0]
+
+    def recover_all_cells_batch(self, cell_ids: Sequence[int],
+                                cells_per_blob: Sequence[Sequence[bytes]]):
+        """The same for several blobs that share one set of known columns:
+        cells_per_blob[b][t] is cell cell_ids[t] of blob b."""
+        ids = _pack_cell_ids(cell_ids)
+        k, n = len(cell_ids), len(cells_per_blob)
+        if n > _MAX_BATCH:
+            raise KzgError(f"recover_all_cells: at most {_MAX_BATCH} blobs a call")
+        for cells in cells_per_blob:
+            if len(cells) != k:
+                raise KzgError(
+                    f"inconsistent array length: {k} cell ids, {len(cells)} cells")
+        if n == 0:
+            return []
+        ce = b"".join(_join("cell", cells, BYTES_PER_CELL)
+                      for cells in cells_per_blob)
+        per_blob = CELLS_PER_EXT_BLOB * BYTES_PER_CELL
+        out = ctypes.create_string_buffer(per_blob * n)
+        rc = self._lib.m3x_kzgc_recover_cells(
+            self._ctx.handle, ids, k, ce, n, out)
+        self._recovered(rc, "recover_all_cells")
+        raw = out.raw
+        return [
+            _split(raw[per_blob * i : per_blob * (i + 1)], BYTES_PER_CELL,
+                   CELLS_PER_EXT_BLOB)
+            for i in range(n)
+        ]
+
+    def recover_all_cells_batch_dev(self, cell_ids: Sequence[int], cells_dev,
+                                    n: int, cells_out_dev):
+        """Device-resident form: cells_dev n*k*2048, blob-major in the order
+        of cell_ids (host) -> cells_out_dev n*262144."""
+        ids = _pack_cell_ids(cell_ids)
+        if not 0 <= n <= _MAX_BATCH:
+            raise KzgError(f"recover_all_cells: at most {_MAX_BATCH} blobs a call")
+        rc = self._lib.m3x_kzgc_recover_cells_dev(
+            self._ctx.handle, ids, len(cell_ids), cells_dev, n, cells_out_dev)
+        self._recovered(rc, "recover_all_cells_dev")
+
+    @staticmethod
+    def _recovered(rc, what):
+        if rc == _ERR_ENCODING:
+            raise KzgError(
+                f"{what}: non-canonical field element, or cells that do not "
+                "lie on one polynomial of degree < 4096")
+        if rc == _ERR_ARG:
+            raise KzgError(f"{what}: bad cell ids or count")
+        if rc != 0:
+            raise RuntimeError(f"{what} failed (rc={rc})")
+
     # ---- lib.rs:187-201 ----
     def verify_cell_proof_batch(self, cells: Sequence[bytes],
                                 proofs: Sequence[bytes],
@@ -431,6 +491,27 @@ class Kzg:
             raise KzgError("verify_cell_proof_batch: this Kzg has no cell "
                            "setup loaded")
         return _pack_cell_batch(cells, proofs, coordinates, commitments)
+
+
+def _pack_cell_ids(cell_ids):
+    """Checked ctypes array of the known cells' numbers."""
+    k = len(cell_ids)
+    if not CELLS_PER_EXT_BLOB // 2 <= k <= CELLS_PER_EXT_BLOB:
+        raise KzgError(
+            f"recover_all_cells: {k} cells, need {CELLS_PER_EXT_BLOB // 2}.."
+            f"{CELLS_PER_EXT_BLOB}")
+    ids = []
+    for c in cell_ids:
+        try:
+            c = int(c)
+        except (TypeError, ValueError):
+            raise KzgError(f"bad cell id {c!r}") from None
+        if not 0 <= c < CELLS_PER_EXT_BLOB:
+            raise KzgError(f"cell id {c} outside 0..{CELLS_PER_EXT_BLOB - 1}")
+        ids.append(c)
+    if len(set(ids)) != k:
+        raise KzgError("recover_all_cells: repeated cell id")
+    return (ctypes.c_uint64 * k)(*ids)
 
 
 def _pack_cell_batch(cells, proofs, coordinates, commitments):

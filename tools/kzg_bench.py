@@ -28,7 +28,12 @@ for n = 1 and 6 blobs (device-resident blobs and cells), and
 verify_cell_proof_batch for n = 6 cells (one column of a 6-blob block), 128
 (every column of one blob) and 768 (6 blobs x 128 columns) from host buffers
 (the call has no device-resident form), under the known-tau test setup.
-Inputs, the reference cells and the proofs [q_c(tau)]G1 are prepared once."""
+Inputs, the reference cells and the proofs [q_c(tau)]G1 are prepared once.
+
+--recover times recover_all_cells, by the same method, for n = 1 and 6 blobs
+over device-resident known cells and outputs, with two patterns of 64 known
+cells: cells 0..63 missing, and 64 random cells missing. The output is
+compared with the reference cells once, before timing. No setup is needed."""
 import argparse
 import ctypes
 import hashlib
@@ -262,6 +267,54 @@ def cells_main(args, fx, ctx, kzg):
     k.close()
 
 
+def recover_main(args, ctx, kzg):
+    import random
+
+    import kzg_cells_ref as C
+    import kzg_ref as K
+
+    k = kzg.Kzg(bytes.fromhex(json.loads(
+        (REPO / "tests" / "golden" / "kzg_fixtures.json").read_text()
+    )["test_setup"]["g2_tau"]), ctx=ctx)
+    ref_cells = []
+    for i in range(6):
+        coef = C.blob_coefficients(K.blob_from_seed(b"kzg-recover-bench-%d" % i))
+        ref_cells.append(
+            [C.cell_to_bytes(c) for c in C.cells_from_coefficients(coef)])
+    patterns = {
+        "first_half_missing": list(range(64, 128)),
+        "random_64_missing": sorted(random.Random(1).sample(range(128), 64)),
+    }
+    for name, ids in patterns.items():
+        for n in (1, 6):
+            cells_d = ctx.upload(b"".join(
+                b"".join(ref_cells[b][c] for c in ids) for b in range(n)))
+            out_d = ctx.alloc(n * 128 * 2048)
+            run = lambda: k.recover_all_cells_batch_dev(ids, cells_d, n, out_d)  # noqa: E731
+            run()
+            got = ctypes.create_string_buffer(n * 128 * 2048)
+            assert ctx._lib.m3x_d2h(ctx.handle, got, out_d, len(got)) == 0
+            assert got.raw == b"".join(b"".join(c) for c in ref_cells[:n]), \
+                "recovered cells differ from the reference"
+            times, kernels = timed(ctx, run, args.reps, args.warmup)
+            med = statistics.median(times)
+            print(json.dumps({
+                "call": "recover_all_cells",
+                "pattern": name,
+                "n_blobs": n,
+                "known_cells": len(ids),
+                "reps": args.reps,
+                "ms_min": round(min(times) * 1e3, 4),
+                "ms_median": round(med * 1e3, 4),
+                "ms_max": round(max(times) * 1e3, 4),
+                "blobs_per_s_median": round(n / med, 2),
+                "kernel_ms_serialised": kernels,
+            }), flush=True)
+            ctx.free(cells_d)
+            ctx.free(out_d)
+    k.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--sizes", default=None)
@@ -271,6 +324,8 @@ def main():
                     help="time commitment and blob-proof computation instead")
     ap.add_argument("--cells", action="store_true",
                     help="time compute_cells and cell-proof batch verification")
+    ap.add_argument("--recover", action="store_true",
+                    help="time recover_all_cells")
     args = ap.parse_args()
     if args.sizes is None:
         args.sizes = "1,6" if args.prove else "1,6,192"
@@ -278,6 +333,8 @@ def main():
     from lighthouse_amd import _native, kzg
 
     fx = json.loads((REPO / "tests" / "golden" / "kzg_fixtures.json").read_text())
+    if args.recover:
+        return recover_main(args, _native.default_ctx(), kzg)
     if args.cells:
         return cells_main(args, fx, _native.default_ctx(), kzg)
     triples = make_triples(fx["test_setup"]["tau_seed"])

@@ -67,8 +67,11 @@ int32_t m3x_abi_version(void);
  * 22 kzgc_decode: canonical check of the cell evaluations, 23 kzgc_combine:
  * challenge powers, row weights and the per-column interpolation,
  * 24 kzgc_recover: the vanishing values and the five transform passes of
- * m3x_kzgc_recover_cells. Cell verification also counts into 10, 13, 14 and
- * 15, whose work it shares). */
+ * m3x_kzgc_recover_cells, 26 bls_sigmsm: the batch signature sum as a
+ * bucket MSM; where it runs, 19 times the signature pairing alone. 25 is
+ * not a slot and stays M3X_ERR_ARG: it was the first id past the table
+ * when the table had 25 entries and is probed as such. Cell
+ * verification also counts into 10, 13, 14 and 15, whose work it shares). */
 int32_t m3x_timing_enable(m3x_ctx *ctx, int32_t on);
 int32_t m3x_kernel_ms(m3x_ctx *ctx, int32_t kernel_id, double *ms,
                       uint64_t *launches);
@@ -177,6 +180,16 @@ int32_t m3x_bls_expand_test(m3x_ctx *ctx, const uint8_t *msg,
 int32_t m3x_bls_h2c_test(m3x_ctx *ctx, const uint8_t *msg, uint32_t msg_len,
                          const uint8_t *dst, uint32_t dst_len,
                          uint8_t out_uncomp[192], uint8_t out_uniform[256]);
+
+/* Test entry for the batch pipeline's signature sum: decompresses the n
+ * signatures, forms sum_i rands[i] * sigs[i] with the bucket MSM
+ * (use_msm != 0) or with the per-set multiplications and the two-stage
+ * reduction (use_msm == 0), and writes the sum as an uncompressed affine
+ * point. Returns 0, or 1 for a sum at infinity (out_uncomp all zero);
+ * M3X_ERR_ENCODING if a signature does not decode. No subgroup check. */
+int32_t m3x_bls_sig_sum_test(m3x_ctx *ctx, const uint8_t *sigs /* n*96 */,
+                             const uint64_t *rands /* n */, uint64_t n,
+                             int32_t use_msm, uint8_t out_uncomp[192]);
 
 int32_t m3x_bls_pk_decompress(m3x_ctx *ctx, const uint8_t *comp /* n*48 */,
                               uint64_t n, uint8_t *uncomp /* n*96 */,

@@ -182,6 +182,17 @@ def _bind(lib):
             ],
         ),
         (
+            "m3x_bls_sig_sum_test",
+            [
+                ctypes.c_void_p,
+                ctypes.c_char_p,
+                ctypes.POINTER(ctypes.c_uint64),
+                ctypes.c_uint64,
+                ctypes.c_int32,
+                ctypes.c_char_p,
+            ],
+        ),
+        (
             "m3x_bls_pk_decompress",
             [
                 ctypes.c_void_p,
@@ -478,12 +489,22 @@ class Ctx:
     KERNEL_NAMES_KZG_RECOVER = [
         "kzgc_recover",  # recover_cells: vanishing values + five passes
     ]
+    # a list of its own: tests/test_kzg_recover_ref.py pins the sum of the
+    # four above. It starts at id 26: id 25 was the first one past the
+    # 25-entry table, is probed as such (tests/test_gpu_kzg_recover.py), and
+    # stays invalid.
+    KERNEL_NAMES_BLS_MSM = [
+        "bls_sigmsm",  # batch signature sum as a bucket MSM (side stream)
+    ]
+    KERNEL_ID_BLS_MSM = 26
 
     def kernel_times(self):
         out = {}
         names = (self.KERNEL_NAMES + self.KERNEL_NAMES_BLS_TAIL
                  + self.KERNEL_NAMES_KZG_CELLS + self.KERNEL_NAMES_KZG_RECOVER)
-        for i, name in enumerate(names):
+        ids = list(enumerate(names)) + list(
+            enumerate(self.KERNEL_NAMES_BLS_MSM, self.KERNEL_ID_BLS_MSM))
+        for i, name in ids:
             ms = ctypes.c_double()
             n = ctypes.c_uint64()
             if self._lib.m3x_kernel_ms(self._h, i, ctypes.byref(ms), ctypes.byref(n)) == 0:

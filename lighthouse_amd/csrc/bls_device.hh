@@ -936,6 +936,13 @@ __device__ inline void g2j_add_aff(g2j &r, const g2j &p, const g2a &q) {
   r.z = z3;
 }
 
+// a stored sig_aff entry (z = 1: affine x, y; z = 0: infinity) as a g2a
+__device__ __forceinline__ void sig_aff_load(g2a &sig, const g2j &sj) {
+  sig.x = sj.x;
+  sig.y = sj.y;
+  sig.inf = g2j_is_inf(sj) ? 1 : 0;
+}
+
 // [k1]P and [k2]P with ONE shared doubling chain of the base (LSB-first
 // double-and-add) — the subgroup-check [|x|]sigma and the batch [r]sigma
 // share sigma's doublings.

@@ -54,6 +54,7 @@ struct BlsWork {
   fp12m *gt_parts; // [1]
   fp12m *sig_gt;   // [1] miller(-g1, sig_sum), written by the side stream
   int *verdict;    // [1]
+  m3x::SigMsmWork msm; // bucket-MSM form of the signature sum
 };
 
 // Where a stage records a malformed input. The batch pipeline has one flag
@@ -265,14 +266,13 @@ __device__ __forceinline__ void h2c_map_lane(uint64_t n, const BlsWork &w) {
   h2f_from_be64(u.c1, uni + 64);
   g2a q;
   sswu_g2(q, u);
-  g2j pt, cleared;
+  g2j pt;
   iso_map_g2_j(pt, q);
-  // cofactor clearing is a homomorphism (h_eff scalar mult + psi), so
-  // clearing each RO point separately at 2n lanes (2 waves/SIMD hiding
-  // the dependent dbl-chain latency) and summing afterwards equals
-  // clearing the sum — the fin pass is then one mixed add per set
-  clear_cofactor_g2j(cleared, pt);
-  w.h2c_pts[lane] = cleared;
+  // not cleared here: cofactor clearing is a homomorphism, so the fin pass
+  // clears the sum of the two points once. (Clearing each point at 2n
+  // lanes halved the per-lane chain but doubled the ~2,700-multiply clear;
+  // with the front of the step throughput-bound that lost: DESIGN.md.)
+  w.h2c_pts[lane] = pt;
 }
 
 // default register budget: the high-occupancy regime (n > latency_max)
@@ -291,13 +291,27 @@ void k_bls_h2c_map_lat(uint64_t n, BlsWork w) {
   h2c_map_lane(n, w);
 }
 
-__global__ __launch_bounds__(64, 1) void k_bls_h2c_fin(uint64_t n,
-                                                       BlsWork w) {
+// fin pass, n lanes: the sum of a message's two iso-mapped points, then
+// the one cofactor clear (two [|x|] chains with a Jacobian base)
+__device__ __forceinline__ void h2c_fin_lane(uint64_t n, const BlsWork &w) {
   uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   g2j s = w.h2c_pts[i];
   g2j_add(s, s, w.h2c_pts[n + i]);
-  w.h2c[i] = s;
+  g2j cleared;
+  clear_cofactor_g2j(cleared, s);
+  w.h2c[i] = cleared;
+}
+
+__global__ __launch_bounds__(64, 1) void k_bls_h2c_fin(uint64_t n,
+                                                       BlsWork w) {
+  h2c_fin_lane(n, w);
+}
+
+// latency-regime register-budget twin (see k_bls_h2c_map_lat)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void k_bls_h2c_fin_lat(uint64_t n, BlsWork w) {
+  h2c_fin_lane(n, w);
 }
 
 // small-batch variant: ONE WAVE PER SET (cooperative miller_w). At tiny n
@@ -500,6 +514,22 @@ __global__ void k_bls_h2c_dst(const uint8_t *__restrict__ msg,
   g2_to_uncomp_dev(a, out);
 }
 
+// one-thread test kernel: a Jacobian G2 point as 192 uncompressed bytes
+// (all zero for infinity, with *is_inf = 1)
+__global__ void k_bls_g2j_uncomp(const g2j *__restrict__ p,
+                                 uint8_t *__restrict__ out,
+                                 int32_t *__restrict__ is_inf) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  g2a a;
+  g2j_to_aff(a, p[0]);
+  *is_inf = a.inf ? 1 : 0;
+  if (a.inf) {
+    for (int i = 0; i < 192; i++) out[i] = 0;
+    return;
+  }
+  g2_to_uncomp_dev(a, out);
+}
+
 // one-thread test kernel: general expand_message_xmd only
 __global__ void k_bls_expand_dst(const uint8_t *__restrict__ msg,
                                  uint32_t msg_len,
@@ -508,13 +538,6 @@ __global__ void k_bls_expand_dst(const uint8_t *__restrict__ msg,
                                  uint8_t *__restrict__ out) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
   expand_message_xmd_gen(msg, msg_len, dst, dst_len, len_in_bytes, out);
-}
-
-// a stored sig_aff entry (z = 1: affine x, y; z = 0: infinity) as a g2a
-__device__ __forceinline__ void sig_aff_load(g2a &sig, const g2j &sj) {
-  sig.x = sj.x;
-  sig.y = sj.y;
-  sig.inf = g2j_is_inf(sj) ? 1 : 0;
 }
 
 // ---- WAVE-SPLIT prepare, latency regime (n <= latency_max): the fused
@@ -555,16 +578,19 @@ void k_bls_sigdec_each(const uint8_t *__restrict__ sigs, uint64_t n,
 // B [|x|]sigma + psi subgroup check, C [r]apk on G1. Every class is
 // wave-uniform, no lane carries more than one chain, and the wave count
 // is 3n/64 — a pure latency win for small and medium batches.
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void k_bls_prep_mults3(const uint8_t *__restrict__ pks,
-                       const uint32_t *__restrict__ offs,
-                       const uint64_t *__restrict__ rands, uint64_t n,
-                       BlsWork w) {
+// The body runs the classes First..Last, n lanes each: A..C is the
+// three-class kernel, B..C the two-class one that goes with the bucket MSM
+// (which forms the sum of the [r_i]sigma_i without any of them), A alone
+// the old signature sum of m3x_bls_sig_sum_test.
+template <int First, int Last>
+__device__ __forceinline__ void prep_mults_lane(
+    const uint8_t *__restrict__ pks, const uint32_t *__restrict__ offs,
+    const uint64_t *__restrict__ rands, uint64_t n, const BlsWork &w) {
   uint64_t lane = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (lane >= 3 * n) return;
-  int cls = lane < n ? 0 : (lane < 2 * n ? 1 : 2);
-  uint64_t i = lane - (uint64_t)cls * n;
-  if (cls == 0) { // A: rsig[i] = [r_i] sigma
+  if (lane >= (uint64_t)(Last - First + 1) * n) return;
+  int cls = First + (lane < n ? 0 : (lane < 2 * n ? 1 : 2));
+  uint64_t i = lane - (uint64_t)(cls - First) * n;
+  if (First == 0 && cls == 0) { // A: rsig[i] = [r_i] sigma
     g2a sig;
     sig_aff_load(sig, w.sig_aff[i]);
     if (sig.inf) { // infinity contributes nothing to the signature sum
@@ -576,7 +602,7 @@ void k_bls_prep_mults3(const uint8_t *__restrict__ pks,
     w.rsig[i] = rs;
     return;
   }
-  if (cls == 1) { // B: deferred psi subgroup check (blst.rs:73-77)
+  if (Last >= 1 && cls == 1) { // B: deferred psi subgroup check (blst.rs:73-77)
     g2a sig;
     sig_aff_load(sig, w.sig_aff[i]);
     if (sig.inf) return; // infinity is a valid element
@@ -585,6 +611,7 @@ void k_bls_prep_mults3(const uint8_t *__restrict__ pks,
     if (!psi_eq_neg(sig, xsig_j)) atomicOr(w.fail, 1);
     return;
   }
+  if (Last < 2) return;
   // C: p_scaled[i] = [r_i] apk
   uint32_t k0 = offs[i], k1 = offs[i + 1];
   if (k1 <= k0) {
@@ -616,6 +643,30 @@ void k_bls_prep_mults3(const uint8_t *__restrict__ pks,
     g1j_mul_be_j(rp, apk, rbe, 8);
   }
   w.p_scaled[i] = rp;
+}
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void k_bls_prep_mults3(const uint8_t *__restrict__ pks,
+                       const uint32_t *__restrict__ offs,
+                       const uint64_t *__restrict__ rands, uint64_t n,
+                       BlsWork w) {
+  prep_mults_lane<0, 2>(pks, offs, rands, n, w);
+}
+
+// classes B and C, 2n lanes: one full round of 2 waves/SIMD at 64k sets
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void k_bls_prep_mults2(const uint8_t *__restrict__ pks,
+                       const uint32_t *__restrict__ offs,
+                       const uint64_t *__restrict__ rands, uint64_t n,
+                       BlsWork w) {
+  prep_mults_lane<1, 2>(pks, offs, rands, n, w);
+}
+
+// class A alone (m3x_bls_sig_sum_test's old path)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void k_bls_prep_rsig(const uint64_t *__restrict__ rands, uint64_t n,
+                     BlsWork w) {
+  prep_mults_lane<0, 0>(nullptr, nullptr, rands, n, w);
 }
 
 // ---- per-set pipeline (m3x_bls_verify_each): SignatureSet::verify() for
@@ -668,6 +719,22 @@ uint64_t latency_max_sets() {
   return 1ull << 18;
 }
 
+// Smallest batch whose signature sum goes through the bucket MSM: below
+// it the MSM's fixed bucket reduction costs more than class A's n chains
+// save (DESIGN.md has the sweep). Read per call, as M3X_SMALL_MILLER is.
+uint64_t sig_msm_min_sets() {
+  if (const char *e = getenv("M3X_SIG_MSM_MIN")) return strtoull(e, nullptr, 10);
+  return 4096;
+}
+
+void carve_sig_msm(m3x::ScratchCarver &c, BlsWork &w, uint64_t n) {
+  w.msm.counts = c.take<uint32_t>(m3x::kSigMsmBuckets);
+  w.msm.cursor = c.take<uint32_t>(m3x::kSigMsmBuckets);
+  w.msm.idx = c.take<uint32_t>(m3x::kSigMsmWindows * n);
+  w.msm.buckets = c.take<g2j>(m3x::kSigMsmBuckets);
+  w.msm.win = c.take<g2j>(m3x::kSigMsmWindows);
+}
+
 // collect the k > 1 sets and sum their keys into w.apk; status == nullptr
 // is the batch pipeline (w.fail), else the per-set one
 void launch_aggregate(m3x_ctx *ctx, const void *pks_dev, const void *offs_dev,
@@ -696,18 +763,22 @@ int launch_h2c(m3x_ctx *ctx, const void *msgs_dev, uint64_t n,
   uint32_t blocks = (uint32_t)((n + 63) / 64);
   m3x::time_begin_s(ctx, M3X_K_BLS_H2C, ctx->stream2);
   if (n > 64) { // split h2c pays at small n too (per-lane chain is ONE
-                // point + clear, vs two points + clear in the fused form)
+                // point, then the clear, vs two points + clear in the fused
+                // form)
     uint32_t blocks2 = (uint32_t)((2 * n + 63) / 64);
     hipLaunchKernelGGL(k_bls_h2c_expand, dim3(blocks), dim3(64), 0,
                        ctx->stream2, (const uint8_t *)msgs_dev, n, w);
-    if (n <= latency_max)
+    if (n <= latency_max) {
       hipLaunchKernelGGL(k_bls_h2c_map_lat, dim3(blocks2), dim3(64), 0,
                          ctx->stream2, n, w);
-    else
+      hipLaunchKernelGGL(k_bls_h2c_fin_lat, dim3(blocks), dim3(64), 0,
+                         ctx->stream2, n, w);
+    } else {
       hipLaunchKernelGGL(k_bls_h2c_map, dim3(blocks2), dim3(64), 0,
                          ctx->stream2, n, w);
-    hipLaunchKernelGGL(k_bls_h2c_fin, dim3(blocks), dim3(64), 0,
-                       ctx->stream2, n, w);
+      hipLaunchKernelGGL(k_bls_h2c_fin, dim3(blocks), dim3(64), 0,
+                         ctx->stream2, n, w);
+    }
   } else {
     hipLaunchKernelGGL(k_bls_h2c, dim3(blocks), dim3(64), 0, ctx->stream2,
                        (const uint8_t *)msgs_dev, n, w);
@@ -769,6 +840,12 @@ int run_verify(m3x_ctx *ctx, const void *msgs_dev, const void *sigs_dev,
                const void *pks_dev, const void *offs_dev,
                const void *rands_dev, uint64_t n, int32_t *out) {
   BlsWork w;
+  uint64_t latency_max = latency_max_sets();
+  // the signature sum as a bucket MSM on the side stream (latency regime
+  // only: the fused k_bls_prepare shares sigma's doubling chain between
+  // [r]sigma and the subgroup check, so there the sum is not a class apart)
+  bool use_msm = n <= latency_max && n >= sig_msm_min_sets() &&
+                 n <= m3x::kSigMsmMaxSets;
   int rc = m3x::carve_scratch(
       ctx, &ctx->scratch_a, &ctx->scratch_a_bytes, [&](m3x::ScratchCarver &c) {
         w.apk = c.take<g1j>(n);
@@ -788,13 +865,13 @@ int run_verify(m3x_ctx *ctx, const void *msgs_dev, const void *sigs_dev,
         w.gt_parts = c.take<fp12m>(1);
         w.sig_gt = c.take<fp12m>(1);
         w.verdict = c.take<int>(1);
+        if (use_msm) carve_sig_msm(c, w, n);
       });
   if (rc != M3X_OK) return rc;
   M3X_HIP_CHECK(hipMemsetAsync(w.fail, 0, 4, ctx->stream));
   M3X_HIP_CHECK(hipMemsetAsync(w.agg_count, 0, 4, ctx->stream));
   uint32_t blocks = (uint32_t)((n + 63) / 64);
   launch_aggregate(ctx, pks_dev, offs_dev, n, w, nullptr);
-  uint64_t latency_max = latency_max_sets();
   m3x::time_begin(ctx, M3X_K_BLS_PREPARE);
   if (n > latency_max) {
     // issue-bound regime: the fused shared-chain kernel does less work
@@ -807,13 +884,33 @@ int run_verify(m3x_ctx *ctx, const void *msgs_dev, const void *sigs_dev,
     // full-register-budget twins
     hipLaunchKernelGGL(k_bls_sigdec_lat, dim3(blocks), dim3(64), 0,
                        ctx->stream, (const uint8_t *)sigs_dev, n, w);
-    uint32_t blocks3 = (uint32_t)((3 * n + 63) / 64);
-    hipLaunchKernelGGL(k_bls_prep_mults3, dim3(blocks3), dim3(64), 0,
-                       ctx->stream, (const uint8_t *)pks_dev,
-                       (const uint32_t *)offs_dev,
-                       (const uint64_t *)rands_dev, n, w);
+    if (use_msm) {
+      // sig_aff is complete: release the MSM, which then shares the GPU
+      // with classes B and C and with h2c
+      M3X_HIP_CHECK(hipEventRecord(ctx->ev_pipe[2], ctx->stream));
+      uint32_t blocks2 = (uint32_t)((2 * n + 63) / 64);
+      hipLaunchKernelGGL(k_bls_prep_mults2, dim3(blocks2), dim3(64), 0,
+                         ctx->stream, (const uint8_t *)pks_dev,
+                         (const uint32_t *)offs_dev,
+                         (const uint64_t *)rands_dev, n, w);
+    } else {
+      uint32_t blocks3 = (uint32_t)((3 * n + 63) / 64);
+      hipLaunchKernelGGL(k_bls_prep_mults3, dim3(blocks3), dim3(64), 0,
+                         ctx->stream, (const uint8_t *)pks_dev,
+                         (const uint32_t *)offs_dev,
+                         (const uint64_t *)rands_dev, n, w);
+    }
   }
   m3x::time_end(ctx, M3X_K_BLS_PREPARE);
+  if (use_msm) {
+    M3X_HIP_CHECK(hipStreamWaitEvent(ctx->stream3, ctx->ev_pipe[2], 0));
+    m3x::time_begin_s(ctx, M3X_K_BLS_SIGMSM, ctx->stream3);
+    rc = m3x::launch_bls_sig_msm(ctx->stream3, n, w.sig_aff,
+                                 (const uint64_t *)rands_dev, w.msm,
+                                 w.sig_sum);
+    if (rc != M3X_OK) return rc;
+    m3x::time_end_s(ctx, M3X_K_BLS_SIGMSM, ctx->stream3);
+  }
   DBG_STEP(ctx, "prepare");
   // h2c is independent of prepare: run it on the second stream so the two
   // ~1-wave/SIMD kernels co-reside (both fit at 2 waves/SIMD by VGPR count)
@@ -845,13 +942,17 @@ int run_verify(m3x_ctx *ctx, const void *msgs_dev, const void *sigs_dev,
   m3x::time_end(ctx, M3X_K_BLS_MILLER);
   DBG_STEP(ctx, "miller");
   // The batch tail is two independent chains:
-  //   main stream : reduce_gt x2                      -> gt_parts
-  //   stream3     : reduce_sig x2 -> sigpair (Miller) -> sig_gt
-  // joined by k_bls_finish. The signature chain reads only rsig (complete
-  // once the prepare kernels are) and is the sole writer of sig_stage,
+  //   main stream : reduce_gt x2                        -> gt_parts
+  //   stream3     : [reduce_sig x2 ->] sigpair (Miller) -> sig_gt
+  // joined by k_bls_finish. stream3 is the sole writer of sig_stage,
   // sig_sum and sig_gt; nothing else touches them until k_bls_finish,
-  // which waits on ev_pipe[1]. It is released after the per-set Miller
-  // kernel. Releasing it right after the prepare kernels was measured and
+  // which waits on ev_pipe[1]. With the MSM path sig_sum is already there:
+  // the MSM ran on stream3 behind ev_pipe[2] (recorded after
+  // k_bls_sigdec_lat, the last writer of sig_aff, its only input besides
+  // rands), and stream order puts k_bls_sigpair after it. Otherwise
+  // reduce_sig x2 form it here from rsig (complete once the prepare
+  // kernels are). Either way the pairing is released after the per-set
+  // Miller kernel. Releasing it right after the prepare kernels was measured and
   // gains nothing: prepare, not h2c, is what the Miller kernel waits for,
   // so the chain then starts together with that kernel, which owns every
   // SIMD's register file — reduce_sig starves and the Miller kernel grows
@@ -860,15 +961,23 @@ int run_verify(m3x_ctx *ctx, const void *msgs_dev, const void *sigs_dev,
   // stream: the verdict read-back below synchronises the main stream,
   // whose k_bls_finish has by then waited for the side stream's last
   // kernel.
-  M3X_HIP_CHECK(hipEventRecord(ctx->ev_pipe[0], ctx->stream));
-  M3X_HIP_CHECK(hipStreamWaitEvent(ctx->stream3, ctx->ev_pipe[0], 0));
+  // M3X_SIGPAIR_EARLY=1 (read per call; MSM path only) drops that wait, so
+  // the pairing follows the MSM at once: the measured alternative.
+  const char *early_env = getenv("M3X_SIGPAIR_EARLY");
+  if (!(use_msm && early_env && early_env[0] == '1')) {
+    M3X_HIP_CHECK(hipEventRecord(ctx->ev_pipe[0], ctx->stream));
+    M3X_HIP_CHECK(hipStreamWaitEvent(ctx->stream3, ctx->ev_pipe[0], 0));
+  }
   uint32_t sblocks = (uint32_t)((n + kReduceThreads - 1) / kReduceThreads);
   if (sblocks > kReduceMaxBlocks) sblocks = kReduceMaxBlocks;
   m3x::time_begin_s(ctx, M3X_K_BLS_SIGPAIR, ctx->stream3);
-  hipLaunchKernelGGL(k_bls_reduce_sig, dim3(sblocks), dim3(kReduceThreads), 0,
-                     ctx->stream3, w.rsig, n, w.sig_stage);
-  hipLaunchKernelGGL(k_bls_reduce_sig, dim3(1), dim3(kReduceThreads), 0,
-                     ctx->stream3, w.sig_stage, (uint64_t)sblocks, w.sig_sum);
+  if (!use_msm) {
+    hipLaunchKernelGGL(k_bls_reduce_sig, dim3(sblocks), dim3(kReduceThreads),
+                       0, ctx->stream3, w.rsig, n, w.sig_stage);
+    hipLaunchKernelGGL(k_bls_reduce_sig, dim3(1), dim3(kReduceThreads), 0,
+                       ctx->stream3, w.sig_stage, (uint64_t)sblocks,
+                       w.sig_sum);
+  }
   hipLaunchKernelGGL(k_bls_sigpair, dim3(1), dim3(64), 0, ctx->stream3, w);
   m3x::time_end_s(ctx, M3X_K_BLS_SIGPAIR, ctx->stream3);
   M3X_HIP_CHECK(hipEventRecord(ctx->ev_pipe[1], ctx->stream3));
@@ -954,6 +1063,65 @@ int32_t m3x_bls_h2c_test(m3x_ctx *ctx, const uint8_t *msg, uint32_t msg_len,
   tmp.download(out_uncomp, pt_d, 192);
   if (out_uniform) tmp.download(out_uniform, uni_d, 256);
   return tmp.sync() ? M3X_OK : M3X_ERR_HIP;
+}
+
+int32_t m3x_bls_sig_sum_test(m3x_ctx *ctx, const uint8_t *sigs,
+                             const uint64_t *rands, uint64_t n,
+                             int32_t use_msm, uint8_t out_uncomp[192]) {
+  if (!ctx || !sigs || !rands || !out_uncomp || n == 0 ||
+      n > m3x::kSigMsmMaxSets)
+    return M3X_ERR_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  M3X_HIP_CHECK(hipSetDevice(ctx->device));
+  BlsWork w = {};
+  int32_t *is_inf = nullptr;
+  uint8_t *out_d = nullptr;
+  int rc = m3x::carve_scratch(
+      ctx, &ctx->scratch_a, &ctx->scratch_a_bytes, [&](m3x::ScratchCarver &c) {
+        w.rsig = c.take<g2j>(n);
+        w.sig_aff = c.take<g2j>(n);
+        w.fail = c.take<int>(1);
+        w.sig_stage = c.take<g2j>(kReduceMaxBlocks);
+        w.sig_sum = c.take<g2j>(1);
+        is_inf = c.take<int32_t>(1);
+        out_d = c.take<uint8_t>(192);
+        carve_sig_msm(c, w, n);
+      });
+  if (rc != M3X_OK) return rc;
+  m3x::DevTemps tmp(ctx->stream);
+  const uint8_t *sigs_d = tmp.upload(sigs, n * 96);
+  const uint64_t *rands_d = tmp.upload(rands, n * 8);
+  if (!tmp.ok()) return M3X_ERR_HIP;
+  M3X_HIP_CHECK(hipMemsetAsync(w.fail, 0, 4, ctx->stream));
+  uint32_t blocks = (uint32_t)((n + 63) / 64);
+  hipLaunchKernelGGL(k_bls_sigdec_lat, dim3(blocks), dim3(64), 0, ctx->stream,
+                     sigs_d, n, w);
+  if (use_msm) {
+    rc = m3x::launch_bls_sig_msm(ctx->stream, n, w.sig_aff, rands_d, w.msm,
+                                 w.sig_sum);
+    if (rc != M3X_OK) {
+      (void)tmp.sync();
+      return rc;
+    }
+  } else {
+    hipLaunchKernelGGL(k_bls_prep_rsig, dim3(blocks), dim3(64), 0, ctx->stream,
+                       rands_d, n, w);
+    uint32_t sblocks = (uint32_t)((n + kReduceThreads - 1) / kReduceThreads);
+    if (sblocks > kReduceMaxBlocks) sblocks = kReduceMaxBlocks;
+    hipLaunchKernelGGL(k_bls_reduce_sig, dim3(sblocks), dim3(kReduceThreads),
+                       0, ctx->stream, w.rsig, n, w.sig_stage);
+    hipLaunchKernelGGL(k_bls_reduce_sig, dim3(1), dim3(kReduceThreads), 0,
+                       ctx->stream, w.sig_stage, (uint64_t)sblocks, w.sig_sum);
+  }
+  hipLaunchKernelGGL(k_bls_g2j_uncomp, dim3(1), dim3(1), 0, ctx->stream,
+                     w.sig_sum, out_d, is_inf);
+  int32_t fail = 1, inf = 0;
+  tmp.download(out_uncomp, out_d, 192);
+  tmp.download(&fail, w.fail, 4);
+  tmp.download(&inf, is_inf, 4);
+  if (!tmp.sync()) return M3X_ERR_HIP;
+  if (fail) return M3X_ERR_ENCODING;
+  return inf ? 1 : 0;
 }
 
 int32_t m3x_bls_sig_aggregate(m3x_ctx *ctx, const uint8_t *sigs, uint64_t n,

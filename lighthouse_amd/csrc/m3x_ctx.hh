@@ -25,13 +25,19 @@ enum m3x_kernel_id {
   M3X_K_KZGP_QUOTIENT = 16, // proof quotient in evaluation form
   M3X_K_KZGP_MSM = 17,      // fixed-base MSM: table look-ups + block sums
   M3X_K_KZGP_FINISH = 18,   // last G1 sum + compression
-  M3X_K_BLS_SIGPAIR = 19,   // signature sum + its Miller loop (stream3)
+  M3X_K_BLS_SIGPAIR = 19,   // signature pairing (stream3); with the old
+                            // path also the signature sum before it
   M3X_K_BLS_EACH = 20,      // per-set pairing check (m3x_bls_verify_each)
   M3X_K_KZGC_NTT = 21,      // compute_cells: the three transform passes
   M3X_K_KZGC_DECODE = 22,   // cell evaluations: canonical check + decode
   M3X_K_KZGC_COMBINE = 23,  // r powers, row weights, column interpolation
   M3X_K_KZGC_RECOVER = 24,  // recover_cells: vanishing values + five passes
-  M3X_K_COUNT = 25
+  // 25 is not a slot: it was the first id past the table when the table
+  // had 25 entries, callers probe it as such (tests/test_gpu_kzg_recover.py
+  // does), and m3x_kernel_ms keeps answering M3X_ERR_ARG for it
+  M3X_K_RESERVED_25 = 25,
+  M3X_K_BLS_SIGMSM = 26,    // signature sum by bucket MSM (stream3)
+  M3X_K_COUNT = 27
 };
 
 struct m3x_ctx {
@@ -93,6 +99,30 @@ namespace m3x {
 void launch_bls_verify_each(hipStream_t st, uint64_t n, const m3xb::g1j *apk,
                             const m3xb::g2j *h2c, const m3xb::g2j *sig_aff,
                             const int32_t *status, int32_t *verdicts);
+
+// m3x_bls_msm.hip: sig_sum[0] = sum r_i * sigma_i by a bucket MSM over
+// unsigned windows of the 64-bit r_i. The window width is this one
+// constant; everything else follows from it.
+constexpr int kSigMsmWindowBits = 8;
+constexpr int kSigMsmWindows = (64 + kSigMsmWindowBits - 1) / kSigMsmWindowBits;
+constexpr int kSigMsmDigits = 1 << kSigMsmWindowBits; // digit 0 is skipped
+constexpr int kSigMsmBuckets = kSigMsmWindows * kSigMsmDigits;
+// largest batch the MSM takes: positions in idx are 32-bit
+constexpr uint64_t kSigMsmMaxSets = (1ull << 32) / kSigMsmWindows - 1;
+struct SigMsmWork {
+  uint32_t *counts;      // [kSigMsmBuckets] entries per (window, digit)
+  uint32_t *cursor;      // [kSigMsmBuckets] start of each bucket in idx, then
+                         // the scatter's write position
+  uint32_t *idx;         // [kSigMsmWindows * n] set indices, sorted by bucket
+  m3xb::g2j *buckets;    // [kSigMsmBuckets] bucket sums
+  m3xb::g2j *win;        // [kSigMsmWindows] [2^(c*w)] * window sum
+};
+// sig_aff as k_bls_sigdec_lat leaves it (z = 1 affine, z = 0 infinity);
+// every launch, and the zeroing of counts, goes on st. Returns 0 or
+// M3X_ERR_HIP.
+int launch_bls_sig_msm(hipStream_t st, uint64_t n, const m3xb::g2j *sig_aff,
+                       const uint64_t *rands, const SigMsmWork &m,
+                       m3xb::g2j *sig_sum);
 
 // ensure scratch buffer has at least `bytes`; returns 0 or M3X_ERR_*
 int ensure_scratch(m3x_ctx *ctx, uint8_t **buf, uint64_t *cur, uint64_t bytes);

@@ -155,7 +155,9 @@ int32_t m3x_timing_enable(m3x_ctx *ctx, int32_t on) {
 
 int32_t m3x_kernel_ms(m3x_ctx *ctx, int32_t kernel_id, double *ms,
                       uint64_t *launches) {
-  if (!ctx || kernel_id < 0 || kernel_id >= M3X_K_COUNT) return M3X_ERR_ARG;
+  if (!ctx || kernel_id < 0 || kernel_id >= M3X_K_COUNT ||
+      kernel_id == M3X_K_RESERVED_25)
+    return M3X_ERR_ARG;
   *ms = ctx->kernel_ms[kernel_id];
   *launches = ctx->kernel_launches[kernel_id];
   return M3X_OK;

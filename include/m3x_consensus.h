@@ -68,7 +68,11 @@ int32_t m3x_abi_version(void);
  * challenge powers, row weights and the per-column interpolation,
  * 24 kzgc_recover: the vanishing values and the five transform passes of
  * m3x_kzgc_recover_cells, 26 bls_sigmsm: the batch signature sum as a
- * bucket MSM; where it runs, 19 times the signature pairing alone. 25 is
+ * bucket MSM; where it runs, 19 times the signature pairing alone,
+ * 27 kzgc_toeplitz: the coefficient pass and the fixed-base Toeplitz sums
+ * of the cell proofs, 28 kzgc_proof_dft: their 128-point G1 transform and
+ * compression (the cells of a cells-and-proofs call count into 21, the
+ * recovery of a recover-and-proofs call into 24). 25 is
  * not a slot and stays M3X_ERR_ARG: it was the first id past the table
  * when the table had 25 entries and is probed as such. Cell
  * verification also counts into 10, 13, 14 and 15, whose work it shares). */
@@ -358,8 +362,9 @@ int32_t m3x_kzg_batch_challenge_test(m3x_ctx *ctx, const uint8_t *cs,
  * omega_8192^bitrev7(c), element i at h_c * omega_64^bitrev6(i): the
  * bit-reversed 8192-point domain, so cells 0..63 are the blob itself
  * (cells_to_blob, lib.rs:203-206, is their concatenation and needs no call).
- * Cell proofs are not computed here (lib.rs:171-185 returns both; in Fulu
- * the proofs arrive with the blob). */
+ * m3x_kzgc_compute_cells gives the cells alone and needs no setup;
+ * m3x_kzgc_compute_cells_and_proofs further down gives both halves of
+ * lib.rs:171-185 and needs the g1_monomial table. */
 
 /* The cells of lib.rs:171-185: blobs n*131072 -> cells_out n*128*2048; needs
  * no setup. M3X_ERR_ENCODING for a non-canonical element; n == 0 is M3X_OK,
@@ -425,14 +430,71 @@ int32_t m3x_kzgc_cell_batch_challenge_test(m3x_ctx *ctx,
  * buffer's contents are unspecified; the context stays usable.
  * Method: the spec's recover_polynomialcoeff, the vanishing polynomial of the
  * missing cells taken by its 128 values per domain instead of being formed;
- * three 8192-point transforms and the forward half of compute_cells. Cell
- * proofs are not recomputed. */
+ * three 8192-point transforms and the forward half of compute_cells. The
+ * proofs come from m3x_kzgc_recover_cells_and_proofs. */
 int32_t m3x_kzgc_recover_cells(m3x_ctx *ctx, const uint64_t *cell_ids, uint64_t k,
                                const uint8_t *cells /* n*k*2048, blob-major */,
                                uint64_t n, uint8_t *cells_out /* n*128*2048 */);
 int32_t m3x_kzgc_recover_cells_dev(m3x_ctx *ctx, const uint64_t *cell_ids /* host */,
                                    uint64_t k, const void *cells_dev, uint64_t n,
                                    void *cells_out_dev);
+
+/* ---- PeerDAS cell proofs (Kzg::compute_cells_and_proofs,
+ * crypto/kzg/src/lib.rs:171-185, the proof half; the spec's
+ * compute_cells_and_kzg_proofs and recover_cells_and_kzg_proofs) ----
+ *
+ * The proof of cell c is [q_c(tau)]G1, q_c = p // (X^64 - y_c) with p the
+ * blob's coefficient list and y_c = h_c^64 = omega_128^bitrev7(c). Method:
+ *   h_m     = sum_j p[j + 64(m+1)] * g1_monomial[j]     m = 0..62
+ *   proof_c = sum_m y_c^m * h_m                         c = 0..127
+ * the 63 sums h_m straight from a fixed-base table over g1_monomial (signed
+ * 4-bit digits, look-ups joined by mixed additions, no doublings), then one
+ * 128-point G1 transform per blob and compression. */
+
+/* lib.rs:171-185 needs the whole g1_monomial list: 4096 x 48B compressed
+ * points in the ceremony file's order (natural order: entry j is
+ * [tau^j]G1). Every point is validated on the device (decodes, in the
+ * subgroup, not infinity; else M3X_ERR_ENCODING and the handle is
+ * unchanged), then the table of [d * 16^j] multiples is built once: about
+ * 200 MB more of device memory per handle (4096 bases, of which the sums
+ * use 4032), freed by m3x_kzg_destroy. One load per handle: a second one is
+ * M3X_ERR_ARG. Independent of m3x_kzgp_load_g1_lagrange and
+ * m3x_kzgc_load_cell_setup. */
+int32_t m3x_kzgc_load_g1_monomial(m3x_ctx *ctx, m3x_kzg *kzg,
+                                 const uint8_t *g1_monomial /* 4096*48, file order */);
+
+/* lib.rs:171-185, n blobs in one call: blobs n*131072 -> cells_out
+ * n*128*2048 (may be NULL: proofs only) and proofs_out n*128*48, the proof
+ * of blob b, cell c at (b*128 + c)*48. With cells_out the cells are
+ * bit-identical to m3x_kzgc_compute_cells. M3X_ERR_ARG, before any launch:
+ * handle without the monomial table, n > 65535, handle of another device.
+ * M3X_ERR_ENCODING: a blob element >= r. n == 0 is M3X_OK, nothing written.
+ * On an error the outputs are unspecified; the context stays usable. */
+int32_t m3x_kzgc_compute_cells_and_proofs(m3x_ctx *ctx, m3x_kzg *kzg,
+                                         const uint8_t *blobs, uint64_t n,
+                                         uint8_t *cells_out,
+                                         uint8_t *proofs_out);
+int32_t m3x_kzgc_compute_cells_and_proofs_dev(m3x_ctx *ctx, m3x_kzg *kzg,
+                                             const void *blobs_dev, uint64_t n,
+                                             void *cells_out_dev,
+                                             void *proofs_out_dev);
+
+/* recover_cells_and_kzg_proofs (the proof half lib.rs:208-216 leaves out):
+ * m3x_kzgc_recover_cells as it stands, then the proof pipeline over the
+ * recovered blobs, which are cells 0..63 of each output, read in place.
+ * Every argument and error rule of m3x_kzgc_recover_cells applies and is
+ * checked first, then the rules of m3x_kzgc_compute_cells_and_proofs.
+ * cells_out n*128*2048 (required), proofs_out n*128*48. */
+int32_t m3x_kzgc_recover_cells_and_proofs(m3x_ctx *ctx, m3x_kzg *kzg,
+                                         const uint64_t *cell_ids, uint64_t k,
+                                         const uint8_t *cells /* n*k*2048 */,
+                                         uint64_t n, uint8_t *cells_out,
+                                         uint8_t *proofs_out);
+int32_t m3x_kzgc_recover_cells_and_proofs_dev(m3x_ctx *ctx, m3x_kzg *kzg,
+                                             const uint64_t *cell_ids /* host */,
+                                             uint64_t k, const void *cells_dev,
+                                             uint64_t n, void *cells_out_dev,
+                                             void *proofs_out_dev);
 
 #ifdef __cplusplus
 }

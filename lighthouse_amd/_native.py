@@ -366,6 +366,34 @@ def _bind(lib):
              ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
              ctypes.c_void_p],
         ),
+        (
+            "m3x_kzgc_load_g1_monomial",
+            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p],
+        ),
+        (
+            "m3x_kzgc_compute_cells_and_proofs",
+            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p,
+             ctypes.c_uint64, ctypes.c_char_p, ctypes.c_char_p],
+        ),
+        (
+            "m3x_kzgc_compute_cells_and_proofs_dev",
+            [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+             ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p],
+        ),
+        (
+            "m3x_kzgc_recover_cells_and_proofs",
+            [ctypes.c_void_p, ctypes.c_void_p,
+             ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint64,
+             ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p,
+             ctypes.c_char_p],
+        ),
+        (
+            "m3x_kzgc_recover_cells_and_proofs_dev",
+            [ctypes.c_void_p, ctypes.c_void_p,
+             ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint64,
+             ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+             ctypes.c_void_p],
+        ),
     ]:
         try:
             fn = getattr(lib, name)
@@ -497,13 +525,22 @@ class Ctx:
         "bls_sigmsm",  # batch signature sum as a bucket MSM (side stream)
     ]
     KERNEL_ID_BLS_MSM = 26
+    # PeerDAS cell proofs, a list of its own again (the lists above are
+    # pinned by existing tests); ids continue after bls_sigmsm
+    KERNEL_NAMES_KZG_CELL_PROOFS = [
+        "kzgc_toeplitz",  # coefficient pass + the 63 fixed-base Toeplitz sums
+        "kzgc_proof_dft",  # 128-point G1 transform + compression
+    ]
+    KERNEL_ID_KZG_CELL_PROOFS = 27
 
     def kernel_times(self):
         out = {}
         names = (self.KERNEL_NAMES + self.KERNEL_NAMES_BLS_TAIL
                  + self.KERNEL_NAMES_KZG_CELLS + self.KERNEL_NAMES_KZG_RECOVER)
         ids = list(enumerate(names)) + list(
-            enumerate(self.KERNEL_NAMES_BLS_MSM, self.KERNEL_ID_BLS_MSM))
+            enumerate(self.KERNEL_NAMES_BLS_MSM, self.KERNEL_ID_BLS_MSM)) + list(
+            enumerate(self.KERNEL_NAMES_KZG_CELL_PROOFS,
+                      self.KERNEL_ID_KZG_CELL_PROOFS))
         for i, name in ids:
             ms = ctypes.c_double()
             n = ctypes.c_uint64()

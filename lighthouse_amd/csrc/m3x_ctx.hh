@@ -37,7 +37,9 @@ enum m3x_kernel_id {
   // does), and m3x_kernel_ms keeps answering M3X_ERR_ARG for it
   M3X_K_RESERVED_25 = 25,
   M3X_K_BLS_SIGMSM = 26,    // signature sum by bucket MSM (stream3)
-  M3X_K_COUNT = 27
+  M3X_K_KZGC_TOEPLITZ = 27,  // cell proofs: coefficient pass + Toeplitz sums
+  M3X_K_KZGC_PROOF_DFT = 28, // cell proofs: 128-point G1 transform + compress
+  M3X_K_COUNT = 29
 };
 
 struct m3x_ctx {

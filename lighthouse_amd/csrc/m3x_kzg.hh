@@ -9,6 +9,17 @@
 #include "bls_device.hh"
 #include "m3x_ctx.hh"
 
+// affine entry of a fixed-base table; no entry is infinity (d * 2^(4j) is
+// never 0 mod r)
+struct g1t {
+  m3xb::fp x, y;
+};
+
+// shape of a fixed-base table over 4096 points (k_kzgp_bases, k_kzgp_table)
+#define KZGP_WINDOWS 64  // 4-bit windows of a 256-bit scalar
+#define KZGP_DIGITS 8    // table multiples d = 1..8
+#define KZGP_TABLE_POINTS ((uint64_t)KZGP_WINDOWS * 4096 * KZGP_DIGITS)
+
 // validated setup: device-resident points of the pairing checks
 struct m3x_kzg {
   int device = 0;
@@ -19,6 +30,9 @@ struct m3x_kzg {
   // cell verification only (m3x_kzgc_load_cell_setup)
   m3xb::g1j *cell_g1 = nullptr; // g1_monomial[0..64), z = 1
   m3xb::g2j *cell_g2 = nullptr; // [0] = -[tau^64]G2, [1] = G2 generator
+  // cell proofs only (m3x_kzgc_load_g1_monomial): the same table shape over
+  // g1_monomial, T[j][i][d-1] = [d * 2^(4j) tau^i]G1, i in natural order
+  struct g1t *mono_table = nullptr;
 };
 
 // The helpers keep internal linkage, as they had inside m3x_kzg.hip: each
@@ -84,4 +98,12 @@ void launch_kzg_sum_g1(hipStream_t st, const m3xb::g1j *in, uint64_t n,
 // when *fail is set
 void launch_kzg_finish(hipStream_t st, m3xb::g1j *sums, int *fail,
                        int *verdict, const m3xb::g2j *g2);
+// k_kzgp_bases: validate 4096 compressed G1 points (decodes, in the subgroup,
+// not infinity; *fail |= 1 otherwise), bases[j * 4096 + e] = [16^j] of entry
+// bitrev12(e) of the list, j = 0..63
+void launch_kzgp_bases(hipStream_t st, const uint8_t *points_dev,
+                       m3xb::g1j *bases, int *fail);
+// k_kzgp_table: table[(j * 4096 + e) * 8 + d - 1] = [d] bases[j * 4096 + e],
+// affine
+void launch_kzgp_table(hipStream_t st, const m3xb::g1j *bases, g1t *table);
 } // namespace m3x

@@ -37,11 +37,6 @@ using namespace m3xf;
 #define KZG_BLOB_BYTES 131072
 #define KZG_MAX_BATCH 65535 // one grid dimension; far above any block's blobs
 
-// affine table entry; no entry is infinity (d * 2^(4j) is never 0 mod r)
-struct g1t {
-  fp x, y;
-};
-
 namespace {
 
 struct KzgWork {
@@ -556,11 +551,9 @@ bool kzg_args_ok(m3x_ctx *ctx, m3x_kzg *kzg, uint64_t n) {
 //   k_kzgp_msm       16 look-ups per lane, 16384 lanes per blob, block sum
 //   k_kzgp_finish    the last 64 partial sums of a blob + g1_compress
 
-#define KZGP_WINDOWS 64  // 4-bit windows of a 256-bit scalar
-#define KZGP_DIGITS 8    // table multiples d = 1..8
+// KZGP_WINDOWS, KZGP_DIGITS and KZGP_TABLE_POINTS: m3x_kzg.hh
 #define KZGP_PER_LANE 16 // windows (look-ups) per MSM lane
 #define KZGP_BLOCKS (KZG_N * (KZGP_WINDOWS / KZGP_PER_LANE) / 256)
-#define KZGP_TABLE_POINTS ((uint64_t)KZGP_WINDOWS * KZG_N * KZGP_DIGITS)
 
 // one lane per Lagrange point, in blob order: element e of a blob pairs
 // with entry bitrev12(e) of the ceremony file's list
@@ -845,6 +838,17 @@ void launch_kzg_finish(hipStream_t st, g1j *sums, int *fail, int *verdict,
   w.verdict = verdict;
   hipLaunchKernelGGL(k_kzg_finish, dim3(1), dim3(64), 0, st, w, g2);
 }
+
+void launch_kzgp_bases(hipStream_t st, const uint8_t *points_dev, g1j *bases,
+                       int *fail) {
+  hipLaunchKernelGGL(k_kzgp_bases, dim3(KZG_N / 64), dim3(64), 0, st,
+                     points_dev, bases, fail);
+}
+
+void launch_kzgp_table(hipStream_t st, const g1j *bases, g1t *table) {
+  hipLaunchKernelGGL(k_kzgp_table, dim3(KZGP_WINDOWS * KZG_N / 64), dim3(64),
+                     0, st, bases, table);
+}
 } // namespace m3x
 
 extern "C" {
@@ -879,6 +883,7 @@ void m3x_kzg_destroy(m3x_kzg *kzg) {
     if (kzg->table) (void)hipFree(kzg->table);
     if (kzg->cell_g1) (void)hipFree(kzg->cell_g1);
     if (kzg->cell_g2) (void)hipFree(kzg->cell_g2);
+    if (kzg->mono_table) (void)hipFree(kzg->mono_table);
   }
   delete kzg;
 }

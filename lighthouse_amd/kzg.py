@@ -2,7 +2,8 @@
 (crypto/kzg/src/lib.rs:62-216): verify_kzg_proof, verify_blob_kzg_proof and
 verify_blob_kzg_proof_batch, the producing half blob_to_kzg_commitment,
 compute_kzg_proof and compute_blob_kzg_proof, and the PeerDAS cell functions
-compute_cells, cells_to_blob, verify_cell_proof_batch and recover_all_cells
+compute_cells, compute_cells_and_kzg_proofs, cells_to_blob,
+verify_cell_proof_batch, recover_all_cells and recover_cells_and_kzg_proofs
 (lib.rs:171-216).
 
 Verification needs one trusted-setup point, [tau]G2 (entry 1 of the
@@ -11,7 +12,9 @@ and proofs also needs the 4096 g1_lagrange points, in the ceremony file's
 order; without them the handle is verification-only. Cell verification
 needs g1_monomial[0..64) and g2_monomial[64] (load_cell_setup, or the
 with_cell_setup constructor); compute_cells and recover_all_cells need no
-setup at all. All byte strings are the spec's big-endian wire forms. Every verify method returns a bool: a
+setup at all; cell proofs (compute_cells_and_kzg_proofs,
+recover_cells_and_kzg_proofs) need the 4096 g1_monomial points
+(load_g1_monomial). All byte strings are the spec's big-endian wire forms. Every verify method returns a bool: a
 proof that does not verify is False; malformed input (bad point encoding, a
 point outside the subgroup, a scalar >= the field modulus, wrong lengths)
 or a producing call without the Lagrange basis raises KzgError, the
@@ -70,7 +73,9 @@ def _split(raw, size, n):
 class Kzg:
     """Trusted setup bound to one GPU context: [tau]G2 for verification,
     plus (optionally) the Lagrange basis for commitments and proofs. The
-    basis costs a one-time table build and about 200 MB of device memory."""
+    basis costs a one-time table build and about 200 MB of device memory;
+    load_g1_monomial (cell proofs) builds a second table of the same shape
+    over g1_monomial, about 200 MB more."""
 
     def __init__(self, g2_tau: bytes, g1_lagrange=None,
                  ctx: Optional[_native.Ctx] = None):
@@ -90,6 +95,7 @@ class Kzg:
             )
         self._has_basis = False
         self._has_cell_setup = False
+        self._has_monomial = False
         self._ctx = ctx or _native.default_ctx()
         self._lib = _native.load()
         self._h = ctypes.c_void_p()
@@ -346,6 +352,121 @@ class Kzg:
             raise RuntimeError(f"m3x_kzgc_load_cell_setup failed (rc={rc})")
         self._has_cell_setup = True
 
+    def load_g1_monomial(self, points):
+        """Load the 4096 g1_monomial points (4096 * 48 bytes, or 4096 byte
+        strings, the ceremony file's order): what cell proofs need. Builds a
+        fixed-base table of about 200 MB of device memory once. A refused
+        list raises KzgError and leaves the handle as it was; one load per
+        handle."""
+        if not isinstance(points, (bytes, bytearray)):
+            if len(points) != FIELD_ELEMENTS_PER_BLOB:
+                raise KzgError(
+                    f"g1_monomial: expected {FIELD_ELEMENTS_PER_BLOB} "
+                    f"points, got {len(points)}"
+                )
+            points = _join("g1_monomial point", points, BYTES_PER_COMMITMENT)
+        points = _check_len("g1_monomial", points,
+                            FIELD_ELEMENTS_PER_BLOB * BYTES_PER_COMMITMENT)
+        if self._has_monomial:
+            raise KzgError("g1_monomial already loaded")
+        rc = self._lib.m3x_kzgc_load_g1_monomial(
+            self._ctx.handle, self._h, points)
+        if rc == _ERR_ENCODING:
+            raise KzgError(
+                "g1_monomial holds a point that is not a valid non-infinity "
+                "G1 subgroup point"
+            )
+        if rc != 0:
+            raise RuntimeError(f"m3x_kzgc_load_g1_monomial failed (rc={rc})")
+        self._has_monomial = True
+
+    def _need_monomial(self, what):
+        if not self._has_monomial:
+            raise KzgError(f"{what}: this Kzg has no g1_monomial loaded")
+
+    # ---- lib.rs:171-185, cells and proofs ----
+    def compute_cells_and_kzg_proofs(self, blob: bytes):
+        """(cells, proofs): the blob's 128 cells and their 128 proofs of 48
+        bytes."""
+        return self.compute_cells_and_kzg_proofs_batch([blob])[0]
+
+    def compute_cells_and_kzg_proofs_batch(self, blobs: Sequence[bytes]):
+        self._need_monomial("compute_cells_and_kzg_proofs")
+        n = len(blobs)
+        if n == 0:
+            return []
+        if n > _MAX_BATCH:
+            raise KzgError(
+                f"compute_cells_and_kzg_proofs: at most {_MAX_BATCH} blobs a call")
+        bl = _join("blob", blobs, BYTES_PER_BLOB)
+        cells = ctypes.create_string_buffer(_BYTES_PER_EXT_BLOB * n)
+        proofs = ctypes.create_string_buffer(_PROOF_BYTES_PER_BLOB * n)
+        rc = self._lib.m3x_kzgc_compute_cells_and_proofs(
+            self._ctx.handle, self._h, bl, n, cells, proofs)
+        self._produced(rc, "compute_cells_and_kzg_proofs")
+        return _split_cells_and_proofs(cells.raw, proofs.raw, n)
+
+    def compute_cells_and_kzg_proofs_batch_dev(self, blobs_dev, n: int,
+                                               cells_out_dev, proofs_out_dev):
+        """Device-resident form: blobs n*131072 -> cells_out_dev n*262144
+        (None: proofs only) and proofs_out_dev n*128*48."""
+        self._need_monomial("compute_cells_and_kzg_proofs")
+        if not 0 <= n <= _MAX_BATCH:
+            raise KzgError(
+                f"compute_cells_and_kzg_proofs: at most {_MAX_BATCH} blobs a call")
+        rc = self._lib.m3x_kzgc_compute_cells_and_proofs_dev(
+            self._ctx.handle, self._h, blobs_dev, n, cells_out_dev,
+            proofs_out_dev)
+        self._produced(rc, "compute_cells_and_kzg_proofs_dev")
+
+    # ---- recover_cells_and_kzg_proofs: lib.rs:208-216 plus the proofs ----
+    def recover_cells_and_kzg_proofs(self, cell_ids: Sequence[int],
+                                     cells: Sequence[bytes]):
+        """(cells, proofs) of a blob from at least 64 of its cells; the
+        argument rules of recover_all_cells."""
+        return self.recover_cells_and_kzg_proofs_batch(cell_ids, [cells])[0]
+
+    def recover_cells_and_kzg_proofs_batch(
+            self, cell_ids: Sequence[int],
+            cells_per_blob: Sequence[Sequence[bytes]]):
+        """The same for several blobs that share one set of known columns."""
+        ids = _pack_cell_ids(cell_ids)
+        self._need_monomial("recover_cells_and_kzg_proofs")
+        k, n = len(cell_ids), len(cells_per_blob)
+        if n > _MAX_BATCH:
+            raise KzgError(
+                f"recover_cells_and_kzg_proofs: at most {_MAX_BATCH} blobs a call")
+        for cells in cells_per_blob:
+            if len(cells) != k:
+                raise KzgError(
+                    f"inconsistent array length: {k} cell ids, {len(cells)} cells")
+        if n == 0:
+            return []
+        ce = b"".join(_join("cell", cells, BYTES_PER_CELL)
+                      for cells in cells_per_blob)
+        out = ctypes.create_string_buffer(_BYTES_PER_EXT_BLOB * n)
+        proofs = ctypes.create_string_buffer(_PROOF_BYTES_PER_BLOB * n)
+        rc = self._lib.m3x_kzgc_recover_cells_and_proofs(
+            self._ctx.handle, self._h, ids, k, ce, n, out, proofs)
+        self._recovered(rc, "recover_cells_and_kzg_proofs")
+        return _split_cells_and_proofs(out.raw, proofs.raw, n)
+
+    def recover_cells_and_kzg_proofs_batch_dev(self, cell_ids: Sequence[int],
+                                               cells_dev, n: int,
+                                               cells_out_dev, proofs_out_dev):
+        """Device-resident form: cells_dev n*k*2048, blob-major in the order
+        of cell_ids (host) -> cells_out_dev n*262144, proofs_out_dev
+        n*128*48."""
+        ids = _pack_cell_ids(cell_ids)
+        self._need_monomial("recover_cells_and_kzg_proofs")
+        if not 0 <= n <= _MAX_BATCH:
+            raise KzgError(
+                f"recover_cells_and_kzg_proofs: at most {_MAX_BATCH} blobs a call")
+        rc = self._lib.m3x_kzgc_recover_cells_and_proofs_dev(
+            self._ctx.handle, self._h, ids, len(cell_ids), cells_dev, n,
+            cells_out_dev, proofs_out_dev)
+        self._recovered(rc, "recover_cells_and_kzg_proofs_dev")
+
     # ---- lib.rs:171-185, the cells only ----
     def compute_cells(self, blob: bytes):
         """The blob's 128 cells of 2048 bytes; cells 0..63 are the blob."""
@@ -491,6 +612,23 @@ class Kzg:
             raise KzgError("verify_cell_proof_batch: this Kzg has no cell "
                            "setup loaded")
         return _pack_cell_batch(cells, proofs, coordinates, commitments)
+
+
+_BYTES_PER_EXT_BLOB = CELLS_PER_EXT_BLOB * BYTES_PER_CELL
+_PROOF_BYTES_PER_BLOB = CELLS_PER_EXT_BLOB * BYTES_PER_PROOF
+
+
+def _split_cells_and_proofs(cells_raw, proofs_raw, n):
+    """[(cells, proofs)] of n blobs from the two output buffers."""
+    return [
+        (
+            _split(cells_raw[_BYTES_PER_EXT_BLOB * i : _BYTES_PER_EXT_BLOB * (i + 1)],
+                   BYTES_PER_CELL, CELLS_PER_EXT_BLOB),
+            _split(proofs_raw[_PROOF_BYTES_PER_BLOB * i : _PROOF_BYTES_PER_BLOB * (i + 1)],
+                   BYTES_PER_PROOF, CELLS_PER_EXT_BLOB),
+        )
+        for i in range(n)
+    ]
 
 
 def _pack_cell_ids(cell_ids):

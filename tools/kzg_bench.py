@@ -33,7 +33,17 @@ Inputs, the reference cells and the proofs [q_c(tau)]G1 are prepared once.
 --recover times recover_all_cells, by the same method, for n = 1 and 6 blobs
 over device-resident known cells and outputs, with two patterns of 64 known
 cells: cells 0..63 missing, and 64 random cells missing. The output is
-compared with the reference cells once, before timing. No setup is needed."""
+compared with the reference cells once, before timing. No setup is needed.
+
+--cellproofs times compute_cells_and_kzg_proofs, by the same method, for
+n = 1 and 6 blobs over device-resident blobs, cells and proofs, under the
+known-tau test setup (g1_monomial[j] = [tau^j]G1 from the CPU oracle). It
+first reports the one-time g1_monomial load (validation + table build) and
+the table's device footprint. Beside each result it prints, from the same
+process, compute_cells of the same n and the kzg_mults kernel time of a blob
+verification of the same n: stage 2 (kzgc_proof_dft) is a serial chain of
+such multiplications and is stated as a multiple of it. The first blob's 128
+proofs are compared with [q_c(tau)]G1 from the oracle once, before timing."""
 import argparse
 import ctypes
 import hashlib
@@ -315,6 +325,89 @@ def recover_main(args, ctx, kzg):
     k.close()
 
 
+def cellproofs_main(args, fx, triples, ctx, kzg):
+    import gen_bls_fixtures as G
+    import kzg_cells_ref as C
+    import kzg_ref as K
+
+    oracle = ctypes.CDLL(str(REPO / "oracle" / "liboracle.so"))
+    seed = fx["test_setup"]["tau_seed"]
+    tau = int.from_bytes(hashlib.sha256(seed.encode()).digest(), "big") % K.R
+    gen = G.g1_uncompressed(G.G1G)
+
+    def g1_mul(k):
+        k %= K.R
+        if k == 0:
+            return K.G1_POINT_AT_INFINITY
+        out = ctypes.create_string_buffer(96)
+        assert oracle.m3x_oracle_bls_g1_mul(gen, k.to_bytes(32, "big"), out) == 0
+        raw = out.raw
+        return G.g1_compress(
+            (int.from_bytes(raw[:48], "big"), int.from_bytes(raw[48:], "big")))
+
+    mono, t = [], 1
+    for _ in range(K.FIELD_ELEMENTS_PER_BLOB):
+        mono.append(g1_mul(t))
+        t = t * tau % K.R
+    mono = b"".join(mono)
+    k = kzg.Kzg(bytes.fromhex(fx["test_setup"]["g2_tau"]), ctx=ctx)
+    t0 = time.perf_counter()
+    k.load_g1_monomial(mono)
+    load_ms = (time.perf_counter() - t0) * 1e3
+    table_bytes = 64 * 4096 * 8 * 96
+    print(json.dumps({
+        "setup_load_ms": round(load_ms, 2),
+        "table_bytes": table_bytes,
+        "table_MB": round(table_bytes / 1e6, 1),
+    }), flush=True)
+    coef = C.blob_coefficients(triples[0][0])
+    want0 = b"".join(
+        g1_mul(C.poly_eval(C.cell_quotient(coef, c), tau)) for c in range(128))
+    for n in (1, 6):
+        ts = [triples[i % 3] for i in range(n)]
+        blobs_d = ctx.upload(b"".join(t[0] for t in ts))
+        cs_d = ctx.upload(b"".join(t[1] for t in ts))
+        ps_d = ctx.upload(b"".join(t[2] for t in ts))
+        cells_d = ctx.alloc(n * 128 * 2048)
+        proofs_d = ctx.alloc(n * 128 * 48)
+
+        def verify():
+            assert k.verify_blob_kzg_proof_batch_dev(blobs_d, cs_d, ps_d, n) is True
+
+        _, vk = timed(ctx, verify, max(4, args.reps // 4), 1)
+        ctimes, _ = timed(
+            ctx, lambda: k.compute_cells_batch_dev(blobs_d, n, cells_d),
+            args.reps, args.warmup)
+        run = lambda: k.compute_cells_and_kzg_proofs_batch_dev(  # noqa: E731
+            blobs_d, n, cells_d, proofs_d)
+        run()
+        got = ctypes.create_string_buffer(n * 128 * 48)
+        assert ctx._lib.m3x_d2h(ctx.handle, got, proofs_d, len(got)) == 0
+        assert got.raw[: 128 * 48] == want0, "proofs differ from the oracle's"
+        times, kernels = timed(ctx, run, args.reps, args.warmup)
+        med = statistics.median(times)
+        mults = vk.get("kzg_mults")
+        dft = kernels.get("kzgc_proof_dft")
+        print(json.dumps({
+            "call": "compute_cells_and_kzg_proofs",
+            "n_blobs": n,
+            "reps": args.reps,
+            "ms_min": round(min(times) * 1e3, 4),
+            "ms_median": round(med * 1e3, 4),
+            "ms_max": round(max(times) * 1e3, 4),
+            "blobs_per_s_median": round(n / med, 2),
+            "kernel_ms_serialised": kernels,
+            "stage1_ms": kernels.get("kzgc_toeplitz"),
+            "stage2_ms": dft,
+            "verify_kzg_mults_ms": mults,
+            "stage2_over_kzg_mults": round(dft / mults, 2) if dft and mults else None,
+            "compute_cells_ms_median": round(statistics.median(ctimes) * 1e3, 4),
+        }), flush=True)
+        for p in (blobs_d, cs_d, ps_d, cells_d, proofs_d):
+            ctx.free(p)
+    k.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--sizes", default=None)
@@ -326,6 +419,8 @@ def main():
                     help="time compute_cells and cell-proof batch verification")
     ap.add_argument("--recover", action="store_true",
                     help="time recover_all_cells")
+    ap.add_argument("--cellproofs", action="store_true",
+                    help="time compute_cells_and_kzg_proofs")
     args = ap.parse_args()
     if args.sizes is None:
         args.sizes = "1,6" if args.prove else "1,6,192"
@@ -341,6 +436,8 @@ def main():
     ctx = _native.default_ctx()
     if args.prove:
         return prove_main(args, fx, triples, ctx, kzg)
+    if args.cellproofs:
+        return cellproofs_main(args, fx, triples, ctx, kzg)
     k = kzg.Kzg(bytes.fromhex(fx["test_setup"]["g2_tau"]), ctx=ctx)
     for n in [int(s) for s in args.sizes.split(",")]:
         ts = [triples[i % 3] for i in range(n)]

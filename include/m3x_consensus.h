@@ -185,6 +185,27 @@ int32_t m3x_bls_h2c_test(m3x_ctx *ctx, const uint8_t *msg, uint32_t msg_len,
                          const uint8_t *dst, uint32_t dst_len,
                          uint8_t out_uncomp[192], uint8_t out_uniform[256]);
 
+/* Test entries for the hash-to-curve square roots (not on the hot path).
+ * Fp2 elements are c0 || c1, 48-byte big-endian each; points are 192
+ * uncompressed bytes (x.c1 || x.c0 || y.c1 || y.c0), all zero for infinity.
+ * fp2_sqrt_test: one lane per element; ok[i] = 1 and out[i]^2 = a[i] for a
+ *   square, ok[i] = 0 and out[i] = 0 otherwise.
+ * sswu_test: per u, SSWU + 3-isogeny + to-affine, no cofactor clear.
+ * h2c_batch_test: hash_to_curve of n 32-byte messages under the product DST
+ *   through the pipeline's own kernels, cofactor cleared: mode 0 the fused
+ *   kernel, mode 1 expand -> map -> fin, mode 2 their latency-regime twins. */
+int32_t m3x_bls_fp2_sqrt_test(m3x_ctx *ctx, const uint8_t *a /* n*96 */,
+                              uint64_t n, uint8_t *out /* n*96 */,
+                              uint8_t *ok /* n */);
+int32_t m3x_bls_sswu_test(m3x_ctx *ctx, const uint8_t *u /* n*96 */,
+                          uint64_t n, uint8_t *out /* n*192 */);
+/* as sswu_test, every u through the exceptional-input branch (sswu_g2_slow) */
+int32_t m3x_bls_sswu_slow_test(m3x_ctx *ctx, const uint8_t *u /* n*96 */,
+                               uint64_t n, uint8_t *out /* n*192 */);
+int32_t m3x_bls_h2c_batch_test(m3x_ctx *ctx, const uint8_t *msgs /* n*32 */,
+                               uint64_t n, int32_t mode,
+                               uint8_t *out /* n*192 */);
+
 /* Test entry for the batch pipeline's signature sum: decompresses the n
  * signatures, forms sum_i rands[i] * sigs[i] with the bucket MSM
  * (use_msm != 0) or with the per-set multiplications and the two-stage

@@ -182,6 +182,34 @@ def _bind(lib):
             ],
         ),
         (
+            "m3x_bls_fp2_sqrt_test",
+            [
+                ctypes.c_void_p,
+                ctypes.c_char_p,
+                ctypes.c_uint64,
+                ctypes.c_char_p,
+                ctypes.c_char_p,
+            ],
+        ),
+        (
+            "m3x_bls_sswu_test",
+            [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p],
+        ),
+        (
+            "m3x_bls_sswu_slow_test",
+            [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p],
+        ),
+        (
+            "m3x_bls_h2c_batch_test",
+            [
+                ctypes.c_void_p,
+                ctypes.c_char_p,
+                ctypes.c_uint64,
+                ctypes.c_int32,
+                ctypes.c_char_p,
+            ],
+        ),
+        (
             "m3x_bls_sig_sum_test",
             [
                 ctypes.c_void_p,

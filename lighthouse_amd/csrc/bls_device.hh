@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "bls_consts.h"
+#include "bls_h2c_consts.h"
 #include "sha256.hh"
 
 namespace m3xb {
@@ -322,17 +323,38 @@ __device__ inline void fp_inv(fp &r, const fp &a) {
   fp_pow_limbs(r, a, e, 6);
 }
 
-// sqrt candidate a^((p+1)/4); returns false if a is not a square
-__device__ inline bool fp_sqrt(fp &r, const fp &a) {
-  // (p+1)/4: p+1 has no carry past limb 0 (p[0]=...aaab)
+__device__ __forceinline__ void fp_sel(fp &r, bool c, const fp &a,
+                                       const fp &b) {
+#pragma unroll
+  for (int i = 0; i < 6; i++) r.v[i] = c ? a.v[i] : b.v[i];
+}
+
+// a^((p-3)/4) and a^((p+1)/4)
+__device__ inline void fp_pow_m3(fp &r, const fp &a) {
+  // (p-3)/4: p[0] = ...aaab so p-3 borrows nothing
+  uint64_t t[6] = {BLS_P[0] - 3, BLS_P[1], BLS_P[2],
+                   BLS_P[3], BLS_P[4], BLS_P[5]};
+  uint64_t e[6];
+#pragma unroll
+  for (int i = 0; i < 6; i++)
+    e[i] = (t[i] >> 2) | (i < 5 ? (t[i + 1] << 62) : 0);
+  fp_pow_limbs(r, a, e, 6);
+}
+__device__ inline void fp_pow_p1(fp &r, const fp &a) {
+  // (p+1)/4: p+1 has no carry past limb 0
   uint64_t t[6] = {BLS_P[0] + 1, BLS_P[1], BLS_P[2],
                    BLS_P[3], BLS_P[4], BLS_P[5]};
   uint64_t e[6];
 #pragma unroll
   for (int i = 0; i < 6; i++)
     e[i] = (t[i] >> 2) | (i < 5 ? (t[i + 1] << 62) : 0);
+  fp_pow_limbs(r, a, e, 6);
+}
+
+// sqrt candidate a^((p+1)/4); returns false if a is not a square
+__device__ inline bool fp_sqrt(fp &r, const fp &a) {
   fp s, s2;
-  fp_pow_limbs(s, a, e, 6);
+  fp_pow_p1(s, a);
   fp_sqr(s2, s);
   if (!fp_eq(s2, a)) return false;
   r = s;
@@ -344,14 +366,7 @@ __device__ inline bool fp_sqrt(fp &r, const fp &a) {
 // Lets callers replace a sqrt-then-invert pair (two 381-bit pows) with
 // one pow + one mul. Returns false for non-squares (s, u then invalid).
 __device__ inline bool fp_sqrt_ui(fp &s, fp &u, const fp &a) {
-  // (p-3)/4: p[0] = ...aaab so p-3 borrows nothing
-  uint64_t t[6] = {BLS_P[0] - 3, BLS_P[1], BLS_P[2],
-                   BLS_P[3], BLS_P[4], BLS_P[5]};
-  uint64_t e[6];
-#pragma unroll
-  for (int i = 0; i < 6; i++)
-    e[i] = (t[i] >> 2) | (i < 5 ? (t[i + 1] << 62) : 0);
-  fp_pow_limbs(u, a, e, 6);
+  fp_pow_m3(u, a);
   fp_mul(s, u, a);
   fp s2;
   fp_sqr(s2, s);
@@ -498,12 +513,48 @@ __device__ __forceinline__ void fp2_mul_xi(fp2 &r, const fp2 &a) {
   r.c1 = t1;
 }
 
+__device__ __forceinline__ void fp2_sel(fp2 &r, bool c, const fp2 &a,
+                                        const fp2 &b) {
+  fp_sel(r.c0, c, a.c0, b.c0);
+  fp_sel(r.c1, c, a.c1, b.c1);
+}
+
+__device__ __forceinline__ void fp2_norm(fp &n, const fp2 &a) {
+  fp t;
+  fp_sqr(n, a.c0);
+  fp_sqr(t, a.c1);
+  fp_add(n, n, t);
+}
+
+// A root of a = a0 + a1 i (a1 != 0) given s with s^2 = N(a): ONE pow and a
+// select, no retry. d = (a0+s)/2, u = d^((p-3)/4), t = u d, so t^2 = +-d.
+// "+": (t, a1 u/2), the textbook form (u = 1/t). "-": d is a non-residue,
+// u t = d^((p-1)/2) = -1 gives 1/t = -u, and (a0+s)(a0-s)/4 = -a1^2/4 makes
+// (-a1 u/2, t) the root that the retry on (a0-s)/2 used to find.
+// Meaningless (not a root) when s^2 != N(a): callers check or know.
+__device__ inline void fp2_sqrt_from_norm_root(fp2 &r, const fp2 &a,
+                                               const fp &s) {
+  fp inv2, d, u, t, h, nh, t2;
+  FP_LOAD_C(inv2, FP_TWO_INV); // constant 2^-1 (generator-emitted)
+  fp_add(d, a.c0, s);
+  fp_mul(d, d, inv2);
+  fp_pow_m3(u, d);
+  fp_mul(t, u, d);
+  fp_mul(h, a.c1, u);
+  fp_mul(h, h, inv2);
+  fp_neg(nh, h);
+  fp_sqr(t2, t);
+  bool plus = fp_eq(t2, d);
+  fp_sel(r.c0, plus, t, nh);
+  fp_sel(r.c1, plus, h, t);
+}
+
 __device__ inline bool fp2_sqrt(fp2 &r, const fp2 &a) {
   if (fp2_is_zero(a)) {
     fp2_zero(r);
     return true;
   }
-  if (fp_is_zero(a.c1)) {
+  if (fp_is_zero(a.c1)) { // rare: the generic path has d = 0 here
     fp s;
     if (fp_sqrt(s, a.c0)) {
       r.c0 = s;
@@ -517,26 +568,11 @@ __device__ inline bool fp2_sqrt(fp2 &r, const fp2 &a) {
     r.c1 = s;
     return true;
   }
-  fp n, s, d, x0, x1, t, u, inv2;
-  fp_sqr(n, a.c0);
-  fp_sqr(t, a.c1);
-  fp_add(n, n, t);
+  fp n, s;
+  fp2_norm(n, a);
   if (!fp_sqrt(s, n)) return false;
-  FP_LOAD_C(inv2, FP_TWO_INV); // constant 2^-1 (generator-emitted)
-  fp_add(d, a.c0, s);
-  fp_mul(d, d, inv2);
-  if (!fp_sqrt_ui(x0, u, d)) {
-    fp_sub(d, a.c0, s);
-    fp_mul(d, d, inv2);
-    if (!fp_sqrt_ui(x0, u, d)) return false;
-  }
-  // x1 = c1/(2*x0) = c1 * u * 2^-1 (u = 1/x0 from the fused pow — no
-  // separate fp_inv)
-  fp_mul(x1, a.c1, u);
-  fp_mul(x1, x1, inv2);
   fp2 cand, sq;
-  cand.c0 = x0;
-  cand.c1 = x1;
+  fp2_sqrt_from_norm_root(cand, a, s);
   fp2_sqr(sq, cand);
   if (!fp2_eq(sq, a)) return false;
   r = cand;
@@ -2078,96 +2114,141 @@ __device__ inline void expand_message_xmd_gen(const uint8_t *msg,
   }
 }
 
-// SSWU tail given 1 + 1/tv already in hand (or the tv=0 constant case
-// signaled by tv_zero): shared by the single and dual entry points.
-__device__ inline void sswu_g2_tail(g2a &out, const fp2 &u, const fp2 &zu2,
-                                    const fp2 &inv_tv_p1, bool tv_zero) {
-  fp2 A, B;
+// SSWU by the definition, with a real inversion: only for the exceptional
+// inputs sswu_g2 hands over (never data-typical). Out of line and entered
+// only after sswu_g2_fast has returned, so its frames (fp2_sqrt, fp2_inv)
+// do not stack on top of the fast path's.
+__device__ __noinline__ void sswu_g2_slow(g2a &out, const fp2 &u) {
+  fp2 A, B, Z, zu2, tv, x1, gx, y, t;
   FP2_LOAD_C(A, SSWU_A);
   FP2_LOAD_C(B, SSWU_B);
-  fp2 x1, gx1, y1, x, y, t;
-  if (tv_zero) {
-    FP2_LOAD_C(x1, SSWU_B_DIV_ZA); // constant B/(Z*A)
-  } else {
-    fp2 nb_over_a;
-    FP2_LOAD_C(nb_over_a, SSWU_NB_DIV_A); // constant -B/A
-    fp2_mul(x1, nb_over_a, inv_tv_p1);
-  }
-  fp2_sqr(gx1, x1);
-  fp2_mul(gx1, gx1, x1);
-  fp2_mul(t, A, x1);
-  fp2_add(gx1, gx1, t);
-  fp2_add(gx1, gx1, B);
-  if (fp2_sqrt(y1, gx1)) {
-    x = x1;
-    y = y1;
-  } else {
-    fp2 x2, gx2;
-    fp2_mul(x2, zu2, x1);
-    fp2_sqr(gx2, x2);
-    fp2_mul(gx2, gx2, x2);
-    fp2_mul(t, A, x2);
-    fp2_add(gx2, gx2, t);
-    fp2_add(gx2, gx2, B);
-    fp2_sqrt(y1, gx2); // must succeed
-    x = x2;
-    y = y1;
-  }
-  if (fp2_sgn0(u) != fp2_sgn0(y)) fp2_neg(y, y);
-  out.x = x;
-  out.y = y;
-  out.inf = 0;
-}
-
-__device__ inline void sswu_g2(g2a &out, const fp2 &u) {
-  fp2 Z, zu2, tv, inv_tv;
   FP2_LOAD_C(Z, SSWU_Z);
   fp2_sqr(zu2, u);
   fp2_mul(zu2, zu2, Z);
   fp2_sqr(tv, zu2);
   fp2_add(tv, tv, zu2);
-  bool tz = fp2_is_zero(tv);
-  fp2_zero(inv_tv);
-  if (!tz) {
-    fp2 one;
-    fp2_inv(inv_tv, tv);
+  if (fp2_is_zero(tv)) {
+    FP2_LOAD_C(x1, SSWU_B_DIV_ZA); // constant B/(Z*A)
+  } else {
+    fp2 nb_over_a, one;
+    FP2_LOAD_C(nb_over_a, SSWU_NB_DIV_A); // constant -B/A
+    fp2_inv(t, tv);
     fp2_one(one);
-    fp2_add(inv_tv, one, inv_tv);
+    fp2_add(t, t, one);
+    fp2_mul(x1, nb_over_a, t);
   }
-  sswu_g2_tail(out, u, zu2, inv_tv, tz);
+#pragma unroll 1
+  for (int c = 0; c < 2; c++) { // x1, then x2 = Z u^2 x1
+    fp2_sqr(gx, x1);
+    fp2_add(gx, gx, A);
+    fp2_mul(gx, gx, x1);
+    fp2_add(gx, gx, B);
+    if (fp2_sqrt(y, gx)) break;
+    fp2_mul(x1, zu2, x1);
+  }
+  if (fp2_sgn0(u) != fp2_sgn0(y)) fp2_neg(y, y);
+  out.x = x1;
+  out.y = y;
+  out.inf = 0;
 }
 
-// both h2c points with ONE shared tv inversion (Montgomery batch): the
-// per-point fp2_inv is a full 381-bit pow, the batching costs 3 muls
-__device__ inline void sswu_g2_dual(g2a out[2], const fp2 u[2]) {
-  fp2 Z, zu2[2], tv[2];
+// Simplified SWU onto E2' with exactly TWO pow chains per point, no
+// inversion, no retry, and the same control flow in every lane
+// (tests/h2c_sqrt_ref.py restates it over exact integers):
+//  * projective x1 = xn/xd, xn = B(tv+1), xd = -A tv (Z A when tv = 0);
+//    a = gn xd = g(x1) xd^4 has the squareness of g(x1)
+//  * pow 1, u1 = N(a)^((p-3)/4): s1 = u1 N(a) is the norm's root when
+//    s1^2 = N(a) (g(x1) square), and 1/N(a) = +-u1^2 by that same test,
+//    whence 1/xd = conj(xd) N(gn)/N(a)
+//  * when the test fails s1^2 = -N(a), and since N(Z) = 5 with -5 a residue,
+//    sqrt N(zu2^3 a) = N(zu2) N(u) sqrt(-5) s1: the norm root for the
+//    second candidate g(x2) xd^4 = zu2^3 a comes for free
+//  * pow 2 inside fp2_sqrt_from_norm_root; y = root/xd^2
+// Returns false, out untouched, for the exceptional inputs.
+__device__ __noinline__ bool sswu_g2_fast(g2a &out, const fp2 &u) {
+  fp2 A, B, Z, zu2, tv, xn, xd, a, t;
+  fp ng, nzu, n;
+  FP2_LOAD_C(A, SSWU_A);
+  FP2_LOAD_C(B, SSWU_B);
   FP2_LOAD_C(Z, SSWU_Z);
-  bool tz[2];
-  for (int i = 0; i < 2; i++) {
-    fp2_sqr(zu2[i], u[i]);
-    fp2_mul(zu2[i], zu2[i], Z);
-    fp2_sqr(tv[i], zu2[i]);
-    fp2_add(tv[i], tv[i], zu2[i]);
-    tz[i] = fp2_is_zero(tv[i]);
+  fp2_sqr(zu2, u);
+  fp2_mul(zu2, zu2, Z);
+  fp2_sqr(tv, zu2);
+  fp2_add(tv, tv, zu2);
+  {
+    fp2 one, za, xd2, gn;
+    fp2_one(one);
+    fp2_add(xn, tv, one);
+    fp2_mul(xn, xn, B);
+    fp2_mul(xd, A, tv);
+    fp2_neg(xd, xd);
+    fp2_mul(za, Z, A);
+    fp2_sel(xd, fp2_is_zero(tv), za, xd);
+    fp2_sqr(xd2, xd);
+    fp2_sqr(gn, xn);
+    fp2_mul(t, A, xd2);
+    fp2_add(gn, gn, t);
+    fp2_mul(gn, gn, xn);
+    fp2_mul(t, xd2, xd);
+    fp2_mul(t, t, B);
+    fp2_add(gn, gn, t); // xn^3 + A xn xd^2 + B xd^3
+    fp2_mul(a, gn, xd);
+    fp2_norm(ng, gn);
+    fp nu;
+    fp2_norm(nzu, zu2);
+    fp2_norm(nu, u);
+    fp_mul(nzu, nzu, nu); // N(zu2) N(u)
   }
-  fp2 inv[2], one;
-  fp2_one(one);
-  if (!tz[0] && !tz[1]) {
-    fp2 prod, pinv;
-    fp2_mul(prod, tv[0], tv[1]);
-    fp2_inv(pinv, prod);
-    fp2_mul(inv[0], pinv, tv[1]);
-    fp2_mul(inv[1], pinv, tv[0]);
-  } else { // rare (crafted u): fall back per point
-    for (int i = 0; i < 2; i++) {
-      fp2_zero(inv[i]);
-      if (!tz[i]) fp2_inv(inv[i], tv[i]);
-    }
+  fp2_norm(n, a);
+  fp u1, s1, chk;
+  fp_pow_m3(u1, n);
+  fp_mul(s1, u1, n);
+  fp_sqr(chk, s1);
+  bool is_sq = fp_eq(chk, n); // g(x1) is a square
+  fp2 sel;
+  fp s;
+  {
+    fp2 a2;
+    fp c5, s2;
+    fp2_sqr(t, zu2);
+    fp2_mul(t, t, zu2);
+    fp2_mul(a2, t, a); // g(x2) xd^4
+    FP_LOAD_C(c5, FP_SQRT_NEG5);
+    fp_mul(s2, nzu, c5);
+    fp_mul(s2, s2, s1);
+    fp2_sel(sel, is_sq, a, a2);
+    fp_sel(s, is_sq, s1, s2);
   }
-  for (int i = 0; i < 2; i++) {
-    fp2_add(inv[i], inv[i], one);
-    sswu_g2_tail(out[i], u[i], zu2[i], inv[i], tz[i]);
+  // g(x1) = 0, or the root's d = 0: never data-typical
+  if (fp_is_zero(n) || fp_is_zero(sel.c1)) return false;
+  // x and 1/xd^2 before the second pow, so little stays live across it
+  fp2 x, xdi2;
+  {
+    fp ninv, nn, k;
+    fp2 xdi, xz;
+    fp_sqr(ninv, u1);
+    fp_neg(nn, ninv);
+    fp_sel(ninv, is_sq, ninv, nn); // 1/N(a)
+    fp_mul(k, ng, ninv);           // 1/N(xd)
+    fp2_conj(xdi, xd);
+    fp2_mul_fp(xdi, xdi, k); // 1/xd
+    fp2_mul(x, xn, xdi);
+    fp2_mul(xz, x, zu2);
+    fp2_sel(x, is_sq, x, xz);
+    fp2_sqr(xdi2, xdi);
   }
+  fp2 root, y;
+  fp2_sqrt_from_norm_root(root, sel, s);
+  fp2_mul(y, root, xdi2);
+  if (fp2_sgn0(u) != fp2_sgn0(y)) fp2_neg(y, y);
+  out.x = x;
+  out.y = y;
+  out.inf = 0;
+  return true;
+}
+
+__device__ __forceinline__ void sswu_g2(g2a &out, const fp2 &u) {
+  if (!sswu_g2_fast(out, u)) sswu_g2_slow(out, u);
 }
 
 // iso_map emitting JACOBIAN coordinates — no inversion at all:
@@ -2284,12 +2365,15 @@ __device__ inline void h2c_g2_from_uniform(g2j &r, const uint8_t uni[256]) {
   h2f_from_be64(u[0].c1, uni + 64);
   h2f_from_be64(u[1].c0, uni + 128);
   h2f_from_be64(u[1].c1, uni + 192);
-  g2a qp[2];
-  sswu_g2_dual(qp, u); // one shared tv inversion for both points
-  g2j s, t;
-  iso_map_g2_j(s, qp[0]); // Jacobian iso: no inversion at all
-  iso_map_g2_j(t, qp[1]);
-  g2j_add(s, s, t);
+  g2j pt[2];
+#pragma unroll 1
+  for (int i = 0; i < 2; i++) {
+    g2a q;
+    sswu_g2(q, u[i]);          // two pows, no inversion to share
+    iso_map_g2_j(pt[i], q);    // Jacobian iso: no inversion at all
+  }
+  g2j s;
+  g2j_add(s, pt[0], pt[1]);
   clear_cofactor_g2j(r, s); // stays Jacobian: consumers (Q-Jacobian
                             // Miller loops) need no inversion at all
 }

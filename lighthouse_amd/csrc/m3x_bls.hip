@@ -530,6 +530,68 @@ __global__ void k_bls_g2j_uncomp(const g2j *__restrict__ p,
   g2_to_uncomp_dev(a, out);
 }
 
+// test kernel, one lane per element: fp2_sqrt of a (c0 || c1, 48-byte
+// big-endian each); ok[i] = 0 with out zeroed for a non-square or a
+// non-canonical input
+__global__ __launch_bounds__(64) void k_bls_fp2_sqrt_test(
+    const uint8_t *__restrict__ in, uint64_t n, uint8_t *__restrict__ out,
+    uint8_t *__restrict__ ok) {
+  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  fp2 a, r;
+  fp2_zero(r);
+  bool good = fp_from_be48(a.c0, in + 96 * i) &&
+              fp_from_be48(a.c1, in + 96 * i + 48);
+  if (good) good = fp2_sqrt(r, a);
+  if (!good) fp2_zero(r);
+  fp_to_be48(r.c0, out + 96 * i);
+  fp_to_be48(r.c1, out + 96 * i + 48);
+  ok[i] = good ? 1 : 0;
+}
+
+// test kernel, one lane per u (c0 || c1 big-endian): SSWU + isogeny +
+// to-affine, no cofactor clear; 192 uncompressed bytes per point (all zero
+// for a non-canonical u or a point at infinity). slow != 0 sends every u
+// through sswu_g2_slow, the branch no ordinary input reaches.
+__global__ __launch_bounds__(64) void k_bls_sswu_test(
+    const uint8_t *__restrict__ in, uint64_t n, int slow,
+    uint8_t *__restrict__ out) {
+  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  fp2 u;
+  g2a q, a;
+  a.inf = 1;
+  if (fp_from_be48(u.c0, in + 96 * i) &&
+      fp_from_be48(u.c1, in + 96 * i + 48)) {
+    g2j pt;
+    if (slow)
+      sswu_g2_slow(q, u);
+    else
+      sswu_g2(q, u);
+    iso_map_g2_j(pt, q);
+    g2j_to_aff(a, pt);
+  }
+  if (a.inf) {
+    for (int b = 0; b < 192; b++) out[192 * i + b] = 0;
+    return;
+  }
+  g2_to_uncomp_dev(a, out + 192 * i);
+}
+
+// test kernel, one lane per point: w.h2c[i] as 192 uncompressed bytes
+__global__ __launch_bounds__(64) void k_bls_h2c_uncomp_test(
+    uint64_t n, BlsWork w, uint8_t *__restrict__ out) {
+  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  g2a a;
+  g2j_to_aff(a, w.h2c[i]);
+  if (a.inf) {
+    for (int b = 0; b < 192; b++) out[192 * i + b] = 0;
+    return;
+  }
+  g2_to_uncomp_dev(a, out + 192 * i);
+}
+
 // one-thread test kernel: general expand_message_xmd only
 __global__ void k_bls_expand_dst(const uint8_t *__restrict__ msg,
                                  uint32_t msg_len,
@@ -1062,6 +1124,96 @@ int32_t m3x_bls_h2c_test(m3x_ctx *ctx, const uint8_t *msg, uint32_t msg_len,
                      msg_len, dst_d, dst_len, pt_d, uni_d);
   tmp.download(out_uncomp, pt_d, 192);
   if (out_uniform) tmp.download(out_uniform, uni_d, 256);
+  return tmp.sync() ? M3X_OK : M3X_ERR_HIP;
+}
+
+int32_t m3x_bls_fp2_sqrt_test(m3x_ctx *ctx, const uint8_t *a, uint64_t n,
+                              uint8_t *out, uint8_t *ok) {
+  if (!ctx || !a || !out || !ok || n == 0 || n > (1u << 20))
+    return M3X_ERR_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  M3X_HIP_CHECK(hipSetDevice(ctx->device));
+  m3x::DevTemps tmp(ctx->stream);
+  const uint8_t *a_d = tmp.upload(a, n * 96);
+  uint8_t *out_d = tmp.alloc(n * 96), *ok_d = tmp.alloc(n);
+  if (!tmp.ok()) return M3X_ERR_HIP;
+  uint32_t blocks = (uint32_t)((n + 63) / 64);
+  hipLaunchKernelGGL(k_bls_fp2_sqrt_test, dim3(blocks), dim3(64), 0,
+                     ctx->stream, a_d, n, out_d, ok_d);
+  tmp.download(out, out_d, n * 96);
+  tmp.download(ok, ok_d, n);
+  return tmp.sync() ? M3X_OK : M3X_ERR_HIP;
+}
+
+static int32_t sswu_test(m3x_ctx *ctx, const uint8_t *u, uint64_t n, int slow,
+                         uint8_t *out) {
+  if (!ctx || !u || !out || n == 0 || n > (1u << 20)) return M3X_ERR_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  M3X_HIP_CHECK(hipSetDevice(ctx->device));
+  m3x::DevTemps tmp(ctx->stream);
+  const uint8_t *u_d = tmp.upload(u, n * 96);
+  uint8_t *out_d = tmp.alloc(n * 192);
+  if (!tmp.ok()) return M3X_ERR_HIP;
+  uint32_t blocks = (uint32_t)((n + 63) / 64);
+  hipLaunchKernelGGL(k_bls_sswu_test, dim3(blocks), dim3(64), 0, ctx->stream,
+                     u_d, n, slow, out_d);
+  tmp.download(out, out_d, n * 192);
+  return tmp.sync() ? M3X_OK : M3X_ERR_HIP;
+}
+
+int32_t m3x_bls_sswu_test(m3x_ctx *ctx, const uint8_t *u, uint64_t n,
+                          uint8_t *out) {
+  return sswu_test(ctx, u, n, 0, out);
+}
+
+int32_t m3x_bls_sswu_slow_test(m3x_ctx *ctx, const uint8_t *u, uint64_t n,
+                               uint8_t *out) {
+  return sswu_test(ctx, u, n, 1, out);
+}
+
+int32_t m3x_bls_h2c_batch_test(m3x_ctx *ctx, const uint8_t *msgs, uint64_t n,
+                               int32_t mode, uint8_t *out) {
+  if (!ctx || !msgs || !out || n == 0 || n > (1u << 20) || mode < 0 ||
+      mode > 2)
+    return M3X_ERR_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  M3X_HIP_CHECK(hipSetDevice(ctx->device));
+  BlsWork w = {};
+  uint8_t *out_d = nullptr;
+  int rc = m3x::carve_scratch(
+      ctx, &ctx->scratch_a, &ctx->scratch_a_bytes, [&](m3x::ScratchCarver &c) {
+        w.h2c = c.take<g2j>(n);
+        w.uni = c.take<uint8_t>(n * 256);
+        w.h2c_pts = c.take<g2j>(2 * n);
+        out_d = c.take<uint8_t>(n * 192);
+      });
+  if (rc != M3X_OK) return rc;
+  m3x::DevTemps tmp(ctx->stream);
+  const uint8_t *msgs_d = tmp.upload(msgs, n * 32);
+  if (!tmp.ok()) return M3X_ERR_HIP;
+  uint32_t blocks = (uint32_t)((n + 63) / 64);
+  uint32_t blocks2 = (uint32_t)((2 * n + 63) / 64);
+  if (mode == 0) {
+    hipLaunchKernelGGL(k_bls_h2c, dim3(blocks), dim3(64), 0, ctx->stream,
+                       msgs_d, n, w);
+  } else {
+    hipLaunchKernelGGL(k_bls_h2c_expand, dim3(blocks), dim3(64), 0,
+                       ctx->stream, msgs_d, n, w);
+    if (mode == 1) {
+      hipLaunchKernelGGL(k_bls_h2c_map, dim3(blocks2), dim3(64), 0,
+                         ctx->stream, n, w);
+      hipLaunchKernelGGL(k_bls_h2c_fin, dim3(blocks), dim3(64), 0,
+                         ctx->stream, n, w);
+    } else {
+      hipLaunchKernelGGL(k_bls_h2c_map_lat, dim3(blocks2), dim3(64), 0,
+                         ctx->stream, n, w);
+      hipLaunchKernelGGL(k_bls_h2c_fin_lat, dim3(blocks), dim3(64), 0,
+                         ctx->stream, n, w);
+    }
+  }
+  hipLaunchKernelGGL(k_bls_h2c_uncomp_test, dim3(blocks), dim3(64), 0,
+                     ctx->stream, n, w, out_d);
+  tmp.download(out, out_d, n * 192);
   return tmp.sync() ? M3X_OK : M3X_ERR_HIP;
 }
 

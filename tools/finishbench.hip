@@ -173,7 +173,8 @@ __global__ __launch_bounds__(64) void k_h2cbench(uint64_t *stamp,
   HSTAMP(2);
   fp2 uu[2] = {u0, u1};
   g2a qp[2];
-  sswu_g2_dual(qp, uu);
+  sswu_g2(qp[0], uu[0]);
+  sswu_g2(qp[1], uu[1]);
   HSTAMP(3);
   g2j s, t;
   iso_map_g2_j(s, qp[0]);
